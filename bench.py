@@ -18,20 +18,35 @@ runs them on the exact-f32 MFMA instead; the JSON's ``config.fp32_products`` nam
 compute weights over fp32 master weights, fp32 LayerNorm statistics / softmax / losses / optimizer;
 its training parity against fp32 is pinned by
 ``tests/test_model_parity_gpu.py::test_bf16_training_tracks_fp32``.
-``--precision both`` (default) measures both, fp32 first; the headline ``value`` / ``dtype`` are the
-fp32 run, the bf16 run is reported under ``"mixed_bf16"``.
+A plain run measures the headline only: it sets up, warms up, times ``--steps`` steps of one precision (fp32
+unless ``--precision bf16``), writes the last step's outputs if ``--dump-outputs DIR`` is given, and prints
+the result line.  Everything else is behind ``--full``:
 
-After the learner, ``--inference`` (default on, rank 0) times the actor's agent step
-(``compute_logp_action``: full policy forward + sampling including the selected-units pointer loop,
-HIP-graph replay) at B = 1 and B = 16 -> ``inference_p50_ms``.  Per-step wall / GPU times of the timed
-steps go to stderr.
+* ``--precision both`` (the ``--full`` default) measures both, fp32 first; the headline ``value`` / ``dtype``
+  are the fp32 run, the bf16 run is reported under ``"mixed_bf16"``;
+* ``--sl`` (default on, rl mode) also times the fp32 SL learner step -> ``"sl_fp32"``;
+* ``--inference`` (default on, rank 0) times the actor's agent step (``compute_logp_action``: full policy
+  forward + sampling including the selected-units pointer loop, HIP-graph replay) at B = 1 and B = 16 ->
+  ``inference_p50_ms``.
 
-Run:  python bench.py --gpus 1 --steps 10 --warmup 3
+Per-step wall / GPU times of the timed steps go to stderr.
+
+``--dump-outputs DIR`` writes what the last timed step of the headline run returned and left behind, as
+``DIR/<name>.npy``: every entry of the step's info dict (``info_<key>.npy``, float64) and a fixed, seeded
+sample of the updated weights (``params_sample.npy``, float32; fp32 masters in the bf16 step).  Batches and
+initial weights are seeded.  The kernels sum with float atomics, so the last bits of a step vary from run to
+run, and a chain of optimizer steps amplifies that to percents; with ``--dump-outputs`` the clock is therefore
+stopped before the last timed step, the trainer is put back to its seeded initial state (on every rank), and
+the clock restarted: that step runs warm and is timed like the others, and what it computes is the same in
+every run to fp32 rounding, so two builds run with the same arguments can be compared output for output.
+
+Run:  python bench.py --gpus 1 --steps 10 --warmup 3 [--full] [--dump-outputs DIR]
       torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
 from __future__ import annotations
 
 import argparse
+import copy
 import gc
 import json
 import os
@@ -68,7 +83,37 @@ def _make_trainer(args, precision, device, mode=None):
                      device=device)
 
 
-def run_learner(args, precision, rank, world, device, host_batches, mode=None):
+DUMP_PARAM_SAMPLE = 1 << 22   # weights sampled by --dump-outputs (16 MB of fp32)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _step_outputs(trainer, info):
+    """The last step's results as host arrays: the info dict and a fixed, seeded sample of the updated weights."""
+    import numpy as np
+    out = {}
+    for k, v in info.items():
+        v = v.detach().double().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        out['info_' + ''.join(c if c.isalnum() else '_' for c in str(k))] = v
+    with torch.no_grad():
+        flat = trainer.master.master.detach() if trainer.master is not None else \
+            torch.cat([p.detach().reshape(-1) for p in trainer.params])
+        n = flat.numel()
+        if n > DUMP_PARAM_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            flat = flat[idx.to(flat.device)]
+        out['params_sample'] = flat.float().cpu().numpy()
+    return out
+
+
+def write_outputs(dirname, outputs):
+    import numpy as np
+    assert sum(a.nbytes for a in outputs.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
+def run_learner(args, precision, rank, world, device, host_batches, mode=None, dump=False):
     """W untimed warm-up steps, then exactly K timed steps between barrier + synchronize pairs."""
     from applestar_amd.parallel import dist as pdist
     from applestar_amd.runtime.prefetch import DevicePrefetcher
@@ -86,6 +131,11 @@ def run_learner(args, precision, rank, world, device, host_batches, mode=None):
             i += 1
 
     it = DevicePrefetcher(source(), device)
+    # --dump-outputs: the seeded initial state (weights, empty optimizer state, step counts), put back before the
+    # last timed step.  The kernels' float atomics make the summation order, hence the last bits of every step,
+    # vary from run to run, and training amplifies that (1e-7 after one step, 1e-2 after 25); a last step that
+    # starts from the initial state computes the same arrays in every run, to rounding
+    initial = copy.deepcopy(trainer.state_dict()) if dump else None
 
     def sync():
         if gpu:
@@ -107,14 +157,26 @@ def run_learner(args, precision, rank, world, device, host_batches, mode=None):
     t0 = time.perf_counter()
     if gpu:
         ev[0].record()
+    paused, last_start = 0.0, None
     for i in range(args.steps):
+        if dump and i == args.steps - 1:      # clock stopped while the initial state is put back
+            sync()
+            tp = time.perf_counter()
+            trainer.load_state_dict(initial)
+            if getattr(trainer, 'derived', None) is not None:
+                trainer.derived.refresh()     # the weights' cached forms rebuilt, as after every optimizer step
+            sync()
+            paused = time.perf_counter() - tp
+            if gpu:
+                last_start = torch.cuda.Event(enable_timing=True)
+                last_start.record()
         h0 = time.perf_counter()
         info = trainer.step(next(it))
         if gpu:
             ev[i + 1].record()
         host_t.append(time.perf_counter() - h0)
     sync()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
     loss = float(info['total_loss'].detach())
     t = torch.tensor([elapsed], dtype=torch.float64, device=device if gpu else 'cpu')
     if world > 1:
@@ -132,7 +194,8 @@ def run_learner(args, precision, rank, world, device, host_batches, mode=None):
         allfp = [torch.zeros_like(fp) for _ in range(world)]
         torch.distributed.all_gather(allfp, fp)
         replicas = all(torch.equal(allfp[0], f) for f in allfp[1:])
-    gpu_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)] if gpu else []
+    gpu_ms = [(last_start if last_start is not None and i == args.steps - 1 else ev[i]).elapsed_time(ev[i + 1])
+              for i in range(args.steps)] if gpu else []
     host_ms = [1000.0 * h for h in host_t]
     if rank == 0:
         _log(f'[{precision}] per-step wall between events (ms): ' + ' '.join(f'{x:.2f}' for x in gpu_ms))
@@ -151,6 +214,8 @@ def run_learner(args, precision, rank, world, device, host_batches, mode=None):
                         'eager_steps': trainer.graph.eager_steps}
                        if getattr(trainer, 'graph', None) is not None else None),
     }
+    if dump and rank == 0:
+        res['outputs'] = _step_outputs(trainer, info)
     del trainer, it, info
     gc.collect()
     if gpu:
@@ -205,20 +270,33 @@ def main():
     ap.add_argument('--unroll', type=int, default=64)
     ap.add_argument('--max-entities', type=int, default=512)
     ap.add_argument('--n-batches', type=int, default=2, help='distinct synthetic batches cycled')
-    ap.add_argument('--precision', choices=['fp32', 'bf16', 'both'], default='both',
-                    help='fp32: like-for-like with the fp32 reference learner; bf16: mixed precision; both: fp32 '
-                         'headline + bf16 reported under "mixed_bf16"')
+    ap.add_argument('--precision', choices=['fp32', 'bf16', 'both'], default=None,
+                    help='fp32 (default): like-for-like with the fp32 reference learner; bf16: mixed precision; both '
+                         '(the --full default, needs --full): fp32 headline + bf16 reported under "mixed_bf16"')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline also measure the other precision, the SL learner step and the actor '
+                         'agent step (--precision both, --sl, --inference); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the last step\'s outputs (info dict, sampled updated weights) '
+                         'of the headline run as DIR/<name>.npy')
     ap.add_argument('--no-native', action='store_true', help='disable HIP kernels (torch-only baseline)')
     ap.add_argument('--mode', choices=['rl', 'sl'], default='rl',
                     help='rl: the headline RL learner step; sl: supervised learner step (reference 384 samples/s/GPU)')
     ap.add_argument('--graph', action='store_true', help='replay the learner step from HIP graphs (runtime/step_graph.py)')
-    ap.add_argument('--inference', type=int, default=1, help='1: also time the actor agent step at B=1 and B=16')
+    ap.add_argument('--inference', type=int, default=1,
+                    help='1 (with --full): also time the actor agent step at B=1 and B=16')
     ap.add_argument('--sl', type=int, default=1,
-                    help='1 (rl mode): also time the fp32 SL learner step on the same config -> "sl_fp32" '
+                    help='1 (with --full, rl mode): also time the fp32 SL learner step on the same config -> "sl_fp32" '
                          '(reference 384 samples/s/GPU)')
     ap.add_argument('--conv-benchmark', type=int, default=-1,
                     help='1/0: force MIOpen find-mode autotuning of convolutions on/off (-1: trainer default)')
     args = ap.parse_args()
+    if args.precision is None:
+        args.precision = 'both' if args.full else 'fp32'
+    if args.precision == 'both' and not args.full:
+        ap.error('--precision both measures a second precision beside the headline: it needs --full')
+    if not args.full:
+        args.sl = args.inference = 0
 
     from applestar_amd.parallel import dist as pdist
     from applestar_amd import ops
@@ -241,7 +319,11 @@ def main():
     host_batches = [pin_tree(make(i)) if gpu else make(i) for i in range(args.n_batches)]
 
     precisions = ['fp32', 'bf16'] if args.precision == 'both' else [args.precision]
-    results = {p: run_learner(args, p, rank, world, device, host_batches) for p in precisions}
+    dump = args.dump_outputs is not None
+    results = {p: run_learner(args, p, rank, world, device, host_batches, dump=dump and p == precisions[0])
+               for p in precisions}
+    if dump and rank == 0:   # the headline run's arrays are already on the host; written before the SL / inference extras
+        write_outputs(args.dump_outputs, results[precisions[0]].pop('outputs'))
     if args.sl and args.mode == 'rl':
         # the supervised learner step (distar/agent/default/sl_learner.py) on the same per-GPU batch, fp32 like the
         # reference's, reported beside the headline so the 384 samples/s/GPU comparison is observed by the driver

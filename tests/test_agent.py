@@ -1,6 +1,7 @@
 """Agent layer: featurization of raw observations, Z selection, action decoding, trajectory assembly,
 pseudo-reward metrics (parity vs the reference metric code), learner collate."""
-import importlib.util
+import json
+import os
 import random
 from functools import partial
 
@@ -16,7 +17,7 @@ from applestar_amd.lib.features import SPATIAL_INFO, ENTITY_INFO, SCALAR_INFO, M
 from applestar_amd.lib.game_data import ACTIONS
 from applestar_amd.lib.metrics import levenshtein_distance, hamming_distance, l2_distance
 
-REF_METRIC = '/root/reference/distar/ctools/torch_utils/metric.py'
+GOLDEN_METRIC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'metric_reference.json')
 
 
 def _env(player_ids=('agent1', 'agent2'), steps=1200, seed=0):
@@ -88,24 +89,26 @@ def test_transform_and_reverse_action_roundtrip():
             assert int(labels['target_unit']) == 4
 
 
-@pytest.mark.skipif(not importlib.util.find_spec('torch'), reason='torch')
 def test_metrics_match_reference():
-    spec = importlib.util.spec_from_file_location('refmetric', REF_METRIC)
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    rng = random.Random(0)
-    for _ in range(200):
-        a = torch.tensor([rng.randint(0, 4) for _ in range(rng.randint(0, 7))], dtype=torch.long)
-        b = torch.tensor([rng.randint(0, 4) for _ in range(rng.randint(0, 7))], dtype=torch.long)
-        assert float(levenshtein_distance(a, b)) == float(m.levenshtein_distance(a, b))
+    """``tests/golden/metric_reference.json`` holds the inputs (200 seeded sequence pairs, one boolean pair) and
+    what the reference's ``levenshtein_distance`` (plain, and with its ``l2_distance`` location cost at
+    spatial_x = 160) and ``hamming_distance`` returned for them."""
+    with open(GOLDEN_METRIC) as f:
+        gold = json.load(f)
+    assert len(gold['cases']) == 200
+    for c in gold['cases']:
+        a = torch.tensor(c['a'], dtype=torch.long)
+        b = torch.tensor(c['b'], dtype=torch.long)
+        assert float(levenshtein_distance(a, b)) == c['levenshtein']
         if len(a) and len(b):
-            la = torch.randint(0, 24320, (len(a),))
-            lb = torch.randint(0, 24320, (len(b),))
-            r = m.levenshtein_distance(a, b, la, lb, partial(m.l2_distance, spatial_x=160))
+            la = torch.tensor(c['loc_a'], dtype=torch.long)
+            lb = torch.tensor(c['loc_b'], dtype=torch.long)
+            r = c['levenshtein_l2']
             assert abs(float(levenshtein_distance(a, b, la, lb, partial(l2_distance, spatial_x=160))) - float(r)) < 1e-5
-    x = torch.randint(0, 2, (5, 30)).bool()
-    y = torch.randint(0, 2, (5, 30)).bool()
-    assert torch.equal(hamming_distance(x, y), m.hamming_distance(x, y))
+    x = torch.tensor(gold['hamming']['x']).bool()
+    y = torch.tensor(gold['hamming']['y']).bool()
+    want = torch.tensor(gold['hamming']['distance'], dtype=getattr(torch, gold['hamming']['dtype'].split('.')[1]))
+    assert torch.equal(hamming_distance(x, y), want)
 
 
 def _run_episode(job_type, steps=900, traj_len=3, value_feature=False, until_full=None):

@@ -1,13 +1,21 @@
 """Extended Adam (utils/optim.py): clip / ignore variants, AdamW, state round trip; parity with the
-reference optimizer for the variants whose reference code runs on this torch version."""
+reference optimizer (recorded results) for the variants whose reference code runs on this torch version."""
 import copy
 import math
 
 import pytest
 import torch
 
-from refutil import reference_available, import_reference
+from refutil import golden
 from applestar_amd.utils.optim import Adam
+
+
+VARIANTS = [dict(grad_clip_type='clip_value', clip_value=0.5),
+            dict(grad_clip_type='clip_norm', clip_value=1.0),
+            dict(grad_ignore_type='ignore_value', ignore_value=1.5),
+            dict(grad_ignore_type='ignore_value', ignore_value=50.0),
+            dict(grad_ignore_type='ignore_norm', ignore_value=2.0),
+            dict(grad_ignore_type='ignore_norm', ignore_value=100.0)]
 
 
 def _params(seed=0, scale=1.0):
@@ -18,29 +26,19 @@ def _params(seed=0, scale=1.0):
     return ps
 
 
-def _ref_adam():
-    import_reference()
-    from distar.ctools.torch_utils.optimizer_util import Adam as RefAdam
-    return RefAdam
-
-
-@pytest.mark.skipif(not reference_available(), reason='reference tree not available')
-@pytest.mark.parametrize('kw', [dict(grad_clip_type='clip_value', clip_value=0.5),
-                                dict(grad_clip_type='clip_norm', clip_value=1.0),
-                                dict(grad_ignore_type='ignore_value', ignore_value=1.5),
-                                dict(grad_ignore_type='ignore_value', ignore_value=50.0),
-                                dict(grad_ignore_type='ignore_norm', ignore_value=2.0),
-                                dict(grad_ignore_type='ignore_norm', ignore_value=100.0)])
+@pytest.mark.parametrize('kw', VARIANTS)
 def test_matches_reference_optimizer(kw):
-    RefAdam = _ref_adam()
-    a, b = _params(1), _params(1)
-    ra = RefAdam(a, lr=0.01, betas=(0.0, 0.99), eps=1e-5, **kw)
+    """One step of the reference's Adam from the same parameters and gradients, recorded in
+    ``tests/golden/ref_adam_<variant>.npz``: its processed gradients and updated parameters."""
+    _, ins, want = golden(f'ref_adam_{VARIANTS.index(kw)}')
+    b = [torch.nn.Parameter(ins[f'p{j}'].clone()) for j in range(2)]   # _params(1), as recorded
+    for j, p in enumerate(b):
+        p.grad = ins[f'g{j}'].clone()
     ob = Adam(b, lr=0.01, betas=(0.0, 0.99), eps=1e-5, **kw)
-    ra.step()
     ob.step()
-    for x, y in zip(a, b):
-        torch.testing.assert_close(x.grad, y.grad)
-        torch.testing.assert_close(x.data, y.data)
+    for j, y in enumerate(b):
+        torch.testing.assert_close(want[f'g{j}'], y.grad)
+        torch.testing.assert_close(want[f'p{j}'], y.data)
 
 
 def test_adamw_matches_torch():

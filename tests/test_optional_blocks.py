@@ -1,24 +1,10 @@
-"""Optional network blocks (models/optional.py): numerics vs the reference modules where the reference
-tree is present (CPU, fp32), plus self-consistency checks that always run."""
+"""Optional network blocks (models/optional.py): numerics vs the reference modules (CPU, fp32; the reference's
+random-init weights, the inputs and its outputs are recorded under tests/golden), plus self-consistency checks."""
 import pytest
 import torch
 
-from refutil import reference_available, import_reference
+from refutil import golden
 from applestar_amd.models import optional as O
-
-needs_ref = pytest.mark.skipif(not reference_available(), reason='reference tree not available')
-
-
-def _ref_module_utils():
-    import_reference()
-    import distar.agent.default.model.module_utils as mu
-    return mu
-
-
-def _ref_lstm():
-    import_reference()
-    import distar.agent.default.model.lstm as rl
-    return rl
 
 
 def test_attention_pool_prefix_matches_sequential_masks():
@@ -41,51 +27,34 @@ def test_attention_pool_prefix_matches_sequential_masks():
             torch.testing.assert_close(got[:, i], exp, atol=1e-5, rtol=1e-5)
 
 
-@needs_ref
 @pytest.mark.parametrize('max_num', [None, 20])
 def test_attention_pool_matches_reference(max_num):
-    mu = _ref_module_utils()
-    torch.manual_seed(1)
-    ref = mu.AttentionPool(16, 2, 24, max_num=max_num)
+    sd, ins, want = golden(f'attention_pool_{max_num}')
     ours = O.AttentionPool(16, 2, 24, max_num=max_num)
-    ours.load_state_dict(ref.state_dict(), strict=True)
-    x = torch.randn(4, 7, 16)
-    mask = (torch.rand(4, 7, 1) > 0.4)
-    num = torch.randint(0, 20, (4,))
-    kw = {'num': num} if max_num else {}
-    torch.testing.assert_close(ours(x, mask=mask, **kw), ref(x, mask=mask.clone(), **kw), atol=1e-5, rtol=1e-5)
+    ours.load_state_dict(sd, strict=True)
+    kw = {'num': ins['num']} if max_num else {}
+    torch.testing.assert_close(ours(ins['x'], mask=ins['mask'], **kw), want['y'], atol=1e-5, rtol=1e-5)
 
 
-@needs_ref
 @pytest.mark.parametrize('method', ['conv-film', 'block-input-film', 'bn-film', 'relu-film', 'block-output-film'])
 def test_filmed_resblock_matches_reference(method):
-    mu = _ref_module_utils()
-    torch.manual_seed(2)
+    sd, ins, want = golden(f'filmed_resblock_{method}')
     kw = dict(with_cond=[True], with_batchnorm=True, condition_method=method, num_extra_channels=2,
               extra_channel_freq=2, num_cond_maps=3)
-    ref = mu.FiLMedResBlock(8, **kw).eval()
     ours = O.FiLMedResBlock(8, **kw).eval()
-    ours.load_state_dict(ref.state_dict(), strict=True)
-    x = torch.randn(2, 8, 5, 6)
-    g, b = torch.randn(2, 8), torch.randn(2, 8)
-    ex, cm = torch.randn(2, 2, 5, 6), torch.randn(2, 3, 5, 6)
-    torch.testing.assert_close(ours(x, g, b, ex, cm), ref(x, g, b, ex, cm), atol=1e-5, rtol=1e-5)
+    ours.load_state_dict(sd, strict=True)
+    got = ours(ins['x'], ins['g'], ins['b'], ins['ex'], ins['cm'])
+    torch.testing.assert_close(got, want['y'], atol=1e-5, rtol=1e-5)
 
 
-@needs_ref
 def test_norm_lstm_matches_reference():
-    mu = _ref_module_utils()
-    torch.manual_seed(3)
-    ref = mu.LSTM(12, 16, 2, norm_type='LN')
+    sd, ins, want = golden('norm_lstm')
     ours = O.NormLSTM(12, 16, 2, norm_type='LN')
-    ours.load_state_dict(ref.state_dict(), strict=True)
-    x = torch.randn(5, 3, 12)
-    h0, c0 = torch.randn(2, 3, 16), torch.randn(2, 3, 16)
-    ro, rs = ref(x, (h0, c0))
-    oo, (oh, oc) = ours(x, (h0, c0))
-    torch.testing.assert_close(oo, ro, atol=1e-5, rtol=1e-5)
-    torch.testing.assert_close(oh, torch.stack([s[0] for s in rs]), atol=1e-5, rtol=1e-5)
-    torch.testing.assert_close(oc, torch.stack([s[1] for s in rs]), atol=1e-5, rtol=1e-5)
+    ours.load_state_dict(sd, strict=True)
+    oo, (oh, oc) = ours(ins['x'], (ins['h0'], ins['c0']))
+    torch.testing.assert_close(oo, want['y'], atol=1e-5, rtol=1e-5)
+    torch.testing.assert_close(oh, want['h'], atol=1e-5, rtol=1e-5)
+    torch.testing.assert_close(oc, want['c'], atol=1e-5, rtol=1e-5)
 
 
 def test_pytorch_lstm_state_formats():
@@ -99,35 +68,25 @@ def test_pytorch_lstm_state_formats():
     assert len(listed) == 3 and listed[0][0].shape == (2, 1, 8)
 
 
-@needs_ref
 @pytest.mark.parametrize('bidirectional', [False, True])
 def test_script_lstm_matches_reference(bidirectional):
-    rl = _ref_lstm()
-    torch.manual_seed(5)
-    ref = rl.script_lstm(6, 8, 2, bidirectional=bidirectional)
+    sd, ins, want = golden(f'script_lstm_{bidirectional}')
     ours = O.script_lstm(6, 8, 2, bidirectional=bidirectional)
-    ours.load_state_dict(ref.state_dict(), strict=True)
-    x = torch.randn(4, 3, 6)
+    ours.load_state_dict(sd, strict=True)
     z = torch.zeros(3, 8)
     st = [[(z, z), (z, z)] if bidirectional else (z, z) for _ in range(2)]
-    ro, _ = ref(x, st)
-    oo, _ = ours(x, st)
-    torch.testing.assert_close(oo, ro, atol=1e-5, rtol=1e-5)
+    oo, _ = ours(ins['x'], st)
+    torch.testing.assert_close(oo, want['y'], atol=1e-5, rtol=1e-5)
 
 
-@needs_ref
 def test_bidirectional_lnlstm_matches_reference():
-    rl = _ref_lstm()
-    torch.manual_seed(6)
-    ref = rl.script_lnlstm(6, 8, 2, bidirectional=True)
+    sd, ins, want = golden('script_lnlstm_bidirectional')
     ours = O.script_lnlstm(6, 8, 2, bidirectional=True)
-    ours.load_state_dict(ref.state_dict(), strict=True)
-    x = torch.randn(4, 3, 6)
+    ours.load_state_dict(sd, strict=True)
     z = torch.zeros(3, 8)
     st = [[(z, z), (z, z)] for _ in range(2)]
-    ro, _ = ref(x, st)
-    oo, _ = ours(x, st)
-    torch.testing.assert_close(oo, ro, atol=1e-4, rtol=1e-4)
+    oo, _ = ours(ins['x'], st)
+    torch.testing.assert_close(oo, want['y'], atol=1e-4, rtol=1e-4)
 
 
 def test_block_builders_key_layout():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end shaped verification on the GPU box (each GPU step under its own time limit, chained so the first
 # failure ends the call):
-#   bench (BENCH_ARGS, default the driver's N=1 call) -> smoke() -> pytest -m gpu (TESTS = test paths / -k
+#   bench (BENCH_ARGS, default the N=1 call with --full: both precisions, SL step, actor step) -> smoke() -> pytest -m gpu (TESTS = test paths / -k
 #   expression, default the whole suite) -> optional rocprofv3 kernel trace of the fp32 step (PROF=1).
 # NOBENCH=1 / NOSMOKE=1 / NOTESTS=1 skip a step.  Outputs under gpurun_out/${TAG:-v}_*.
 set -o pipefail
@@ -9,7 +9,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 mkdir -p gpurun_out
 T=${TAG:-v}
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 ${BENCH_TIMEOUT:-400} python -u bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} \
+  timeout -k 10 ${BENCH_TIMEOUT:-400} python -u bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5 --full} \
     > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || { echo bench failed; tail -20 gpurun_out/${T}_bench.err; exit 1; }
   cat gpurun_out/${T}_bench.json
 fi
