@@ -437,7 +437,7 @@ as::SpatialPlanes make_planes(const std::vector<at::Tensor>& planes, const std::
 std::vector<at::Tensor> spatial_embed_fwd(const std::vector<at::Tensor>& planes, const std::vector<at::Tensor>& effects,
                                           const at::Tensor& w_dense, const at::Tensor& bias, const at::Tensor& rows,
                                           const at::Tensor& ex, const at::Tensor& ey, const at::Tensor& entity_num,
-                                          int64_t out_dtype) {
+                                          int64_t out_dtype, bool ordered) {
   auto sp = make_planes(planes, effects);
   const int64_t B = planes[0].size(0), H = planes[0].size(1), W = planes[0].size(2), HW = H * W;
   const int64_t L = effects[0].size(1);
@@ -453,14 +453,15 @@ std::vector<at::Tensor> spatial_embed_fwd(const std::vector<at::Tensor>& planes,
   as::spatial_embed_fused(sp, w_dense.data_ptr<float>(), bias.data_ptr<float>(), rows.data_ptr(), dt(rows),
                           ex.data_ptr<uint8_t>(), ey.data_ptr<uint8_t>(), entity_num.data_ptr<int64_t>(),
                           out.data_ptr(), dt(out), static_cast<int>(B), static_cast<int>(rows.size(1)),
-                          static_cast<int>(H), static_cast<int>(W), static_cast<int>(L), stream());
+                          static_cast<int>(H), static_cast<int>(W), static_cast<int>(L), stream(), ordered);
   return {at::Tensor(), out};
 }
 
 // relu(embed) -> max_pool2x2 fused: {pooled [B,H/2,W/2,32] bf16, pos [B,H/2,W/2,32] uint8}
 std::vector<at::Tensor> spatial_embed_pool_fwd(const std::vector<at::Tensor>& planes, const std::vector<at::Tensor>& effects,
                                                const at::Tensor& w_dense, const at::Tensor& bias, const at::Tensor& rows,
-                                               const at::Tensor& ex, const at::Tensor& ey, const at::Tensor& entity_num) {
+                                               const at::Tensor& ex, const at::Tensor& ey, const at::Tensor& entity_num,
+                                               bool ordered) {
   auto sp = make_planes(planes, effects);
   const int64_t B = planes[0].size(0), H = planes[0].size(1), W = planes[0].size(2);
   const int64_t L = effects[0].size(1);
@@ -481,7 +482,7 @@ std::vector<at::Tensor> spatial_embed_pool_fwd(const std::vector<at::Tensor>& pl
                          ey.data_ptr<uint8_t>(), entity_num.data_ptr<int64_t>(), pooled.data_ptr(),
                          pos.data_ptr<uint8_t>(), static_cast<int>(B), static_cast<int>(rows.size(1)),
                          static_cast<int>(H), static_cast<int>(W), static_cast<int>(L), stream(),
-                         rows.scalar_type() == at::kFloat);
+                         rows.scalar_type() == at::kFloat, ordered);
   return {pooled, pos};
 }
 
@@ -851,12 +852,32 @@ at::Tensor entity_mean_pool(const at::Tensor& x, const at::Tensor& valid, const 
   return out;
 }
 
-at::Tensor table_grad(const at::Tensor& src, const at::Tensor& idx, int64_t V) {  // src [U,D], idx [U] int64
+namespace {
+// the order-fixed small-table sum (ordered.hip): per-workgroup partials over fixed row ranges + column_reduce;
+// mask null: table_grad (rows outside [0, V) skipped), else embed_relu_bwd (idx clamped, src counted where mask > 0)
+at::Tensor table_grad_ordered(const at::Tensor& src, const at::Tensor* mask, const at::Tensor& idx, int idt, int64_t V,
+                              bool single) {
+  const int64_t U = src.size(0), D = src.size(1);
+  if (U == 0) return at::zeros({V, D}, src.options().dtype(at::kFloat));
+  const int blocks = as::table_grad_ordered_blocks(U, single);
+  auto out = at::empty({V, D}, src.options().dtype(at::kFloat));
+  auto part = blocks > 1 ? at::empty({blocks, V * D}, out.options()) : out;
+  as::table_grad_ordered(src.data_ptr(), mask ? mask->data_ptr() : nullptr, dt(src), idx.data_ptr(), idt,
+                         part.data_ptr<float>(), U, static_cast<int>(V), static_cast<int>(D), blocks, stream());
+  if (blocks > 1)
+    as::column_reduce(part.data_ptr<float>(), out.data_ptr<float>(), blocks, static_cast<int>(V * D), stream());
+  return out;
+}
+}  // namespace
+
+// src [U,D], idx [U] int64; ordered: the deterministic mode's fixed summation order
+at::Tensor table_grad(const at::Tensor& src, const at::Tensor& idx, int64_t V, bool ordered) {
   check_cuda(src, "src");
   check_cuda(idx, "idx");
   TORCH_CHECK(src.dim() == 2 && idx.scalar_type() == at::kLong && idx.numel() == src.size(0), "table_grad: shapes");
   TORCH_CHECK(V * src.size(1) <= 16384, "table_grad: table too large for LDS accumulation");
   c10::hip::HIPGuard g(src.device().index());
+  if (ordered) return table_grad_ordered(src, nullptr, idx, 0, V, false);
   auto out = at::zeros({V, src.size(1)}, src.options().dtype(at::kFloat));
   as::table_grad(src.data_ptr(), dt(src), idx.data_ptr<int64_t>(), out.data_ptr<float>(), src.size(0), V, src.size(1),
                  stream());
@@ -891,7 +912,8 @@ at::Tensor embed_relu_fwd(const at::Tensor& table, const at::Tensor& idx) {
 }
 
 // d table (fp32 [V, D]) of embed_relu_fwd: rows of dout masked by out > 0, summed per (clamped) index
-at::Tensor embed_relu_bwd(const at::Tensor& dout, const at::Tensor& out, const at::Tensor& idx, int64_t V) {
+at::Tensor embed_relu_bwd(const at::Tensor& dout, const at::Tensor& out, const at::Tensor& idx, int64_t V,
+                          bool ordered) {
   check_cuda(dout, "dout");
   TORCH_CHECK(dout.sizes() == out.sizes() && dout.scalar_type() == out.scalar_type() && dout.is_contiguous() &&
                   out.is_contiguous() && out.dim() == 2 && idx.numel() == out.size(0) && idx.is_contiguous(),
@@ -900,6 +922,7 @@ at::Tensor embed_relu_bwd(const at::Tensor& dout, const at::Tensor& out, const a
   c10::hip::HIPGuard g(out.device().index());
   const long U = out.size(0), D = out.size(1);
   const bool direct = U * D <= 2048;
+  if (ordered) return table_grad_ordered(dout, &out, idx, idx_dtype_code(idx), V, direct);
   auto dtab = direct ? at::empty({V, D}, out.options().dtype(at::kFloat))
                      : at::zeros({V, D}, out.options().dtype(at::kFloat));
   as::embed_relu_bwd(dout.data_ptr(), out.data_ptr(), dt(out), idx.data_ptr(), idx_dtype_code(idx),
@@ -1713,7 +1736,7 @@ std::vector<at::Tensor> bo_encoder_fwd(const at::Tensor& bo, const at::Tensor& l
 
 // -> flat fp32 parameter gradient [kBoGradSize] in the params order
 at::Tensor bo_encoder_bwd(const at::Tensor& bo, const at::Tensor& loc, const std::vector<at::Tensor>& params,
-                          const at::Tensor& save, const at::Tensor& dmean) {
+                          const at::Tensor& save, const at::Tensor& dmean, bool ordered) {
   check_cuda(dmean, "dmean");
   const int64_t B = bo.size(0);
   TORCH_CHECK(dmean.scalar_type() == at::kFloat && dmean.is_contiguous() && dmean.numel() == B * 64,
@@ -1726,7 +1749,7 @@ at::Tensor bo_encoder_bwd(const at::Tensor& bo, const at::Tensor& loc, const std
   const int reps = static_cast<int>(std::min<int64_t>(B, 32));
   auto rep = at::zeros({reps, as::kBoGradSize}, dmean.options());
   as::bo_encoder_bwd(bo.data_ptr(), loc.data_ptr(), idx_code(bo), w, wdt, save.data_ptr<float>(),
-                     dmean.data_ptr<float>(), rep.data_ptr<float>(), B, reps, stream());
+                     dmean.data_ptr<float>(), rep.data_ptr<float>(), B, reps, stream(), ordered);
   auto grad = at::empty({as::kBoGradSize}, dmean.options());
   as::column_reduce(rep.data_ptr<float>(), grad.data_ptr<float>(), reps, as::kBoGradSize, stream());
   return grad;
@@ -2106,7 +2129,8 @@ std::vector<at::Tensor> gate_chain_f32(const at::Tensor& x, const std::vector<at
 // -> {info [rl_loss_info_size(F)], dalp, dent, dkl [6,T,B], dv [F,T+1,B]}
 std::vector<at::Tensor> rl_loss(const at::Tensor& alp, const at::Tensor& blp, const at::Tensor& hm, const at::Tensor& ent,
                                 const at::Tensor& kl, const at::Tensor& v, const at::Tensor& r, const at::Tensor& wm,
-                                const at::Tensor& atflag, const at::Tensor& sc, int64_t upgo_f, bool only_value) {
+                                const at::Tensor& atflag, const at::Tensor& sc, int64_t upgo_f, bool only_value,
+                                bool ordered) {
   for (const at::Tensor* t : {&alp, &blp, &hm, &ent, &kl, &v, &r, &wm, &atflag, &sc}) {
     check_cuda(*t, "rl_loss operand");
     TORCH_CHECK(t->scalar_type() == at::kFloat, "rl_loss: fp32 operands");
@@ -2122,12 +2146,79 @@ std::vector<at::Tensor> rl_loss(const at::Tensor& alp, const at::Tensor& blp, co
   c10::hip::HIPGuard g(alp.device().index());
   auto info = at::empty({as::rl_loss_info_size(static_cast<int>(F))}, alp.options());
   auto dalp = at::empty_like(alp), dent = at::empty_like(alp), dkl = at::empty_like(alp), dv = at::empty_like(v);
-  as::rl_loss(alp.data_ptr<float>(), blp.data_ptr<float>(), hm.data_ptr<float>(), ent.data_ptr<float>(),
-              kl.data_ptr<float>(), v.data_ptr<float>(), r.data_ptr<float>(), wm.data_ptr<float>(),
-              atflag.data_ptr<float>(), sc.data_ptr<float>(), static_cast<int>(F), static_cast<int>(T),
-              static_cast<int>(B), static_cast<int>(upgo_f), only_value ? 1 : 0, dalp.data_ptr<float>(),
-              dent.data_ptr<float>(), dkl.data_ptr<float>(), dv.data_ptr<float>(), info.data_ptr<float>(), stream());
+  (ordered ? as::rl_loss_ordered : as::rl_loss)(
+      alp.data_ptr<float>(), blp.data_ptr<float>(), hm.data_ptr<float>(), ent.data_ptr<float>(),
+      kl.data_ptr<float>(), v.data_ptr<float>(), r.data_ptr<float>(), wm.data_ptr<float>(),
+      atflag.data_ptr<float>(), sc.data_ptr<float>(), static_cast<int>(F), static_cast<int>(T),
+      static_cast<int>(B), static_cast<int>(upgo_f), only_value ? 1 : 0, dalp.data_ptr<float>(),
+      dent.data_ptr<float>(), dkl.data_ptr<float>(), dv.data_ptr<float>(), info.data_ptr<float>(), stream());
   return {info, dalp, dent, dkl, dv};
+}
+
+// ---------------------------------------------------------------- ordered gather / scatter (ordered.hip)
+// key [B, N1, C] fp32 / bf16, labels [B, S] int64 -> key rows [B, S, C] (labels clamped to [0, N1))
+at::Tensor gather_steps_fwd(const at::Tensor& key, const at::Tensor& labels) {
+  check_cuda(key, "key");
+  check_cuda(labels, "labels");
+  TORCH_CHECK(key.dim() == 3 && labels.dim() == 2 && labels.size(0) == key.size(0) && key.size(1) >= 1 &&
+                  labels.scalar_type() == at::kLong, "gather_steps: key [B, N1, C], labels [B, S] int64");
+  c10::hip::HIPGuard g(key.device().index());
+  auto out = at::empty({key.size(0), labels.size(1), key.size(2)}, key.options());
+  as::gather_steps_fwd(key.data_ptr(), dt(key), labels.data_ptr<int64_t>(), out.data_ptr(), key.size(0),
+                       static_cast<int>(key.size(1)), static_cast<int>(labels.size(1)), static_cast<int>(key.size(2)),
+                       stream());
+  return out;
+}
+
+// dkey [B, N1, C] (dout's dtype): per row the fp32 sum of dout [B, S, C] over the steps naming it, in ascending step
+at::Tensor gather_steps_bwd(const at::Tensor& dout, const at::Tensor& labels, int64_t N1) {
+  check_cuda(dout, "dout");
+  check_cuda(labels, "labels");
+  TORCH_CHECK(dout.dim() == 3 && labels.dim() == 2 && labels.size(0) == dout.size(0) &&
+                  labels.size(1) == dout.size(1) && labels.scalar_type() == at::kLong && N1 >= 1,
+              "gather_steps_bwd: dout [B, S, C], labels [B, S] int64");
+  TORCH_CHECK(N1 * dout.size(2) < (1LL << 31) && dout.size(0) < 65536, "gather_steps_bwd: grid");
+  c10::hip::HIPGuard g(dout.device().index());
+  auto dkey = at::empty({dout.size(0), N1, dout.size(2)}, dout.options());
+  as::gather_steps_bwd(dout.data_ptr(), dt(dout), labels.data_ptr<int64_t>(), dkey.data_ptr(), dout.size(0),
+                       static_cast<int>(N1), static_cast<int>(dout.size(1)), static_cast<int>(dout.size(2)), stream());
+  return dkey;
+}
+
+namespace {
+void check_scatter_conn(const at::Tensor& t, const at::Tensor& x, const at::Tensor& y, int64_t B, int64_t U) {
+  check_cuda(t, "scatter_connection operand");
+  check_cuda(x, "x");
+  check_cuda(y, "y");
+  TORCH_CHECK(x.numel() == B * U && y.numel() == B * U, "scatter_connection: x / y [B, U]");
+  TORCH_CHECK(U <= as::scatter_conn_max_units(), "scatter_connection: at most ", as::scatter_conn_max_units(),
+              " units per observation");
+}
+}  // namespace
+
+// proj [B, U, C] fp32 / bf16, x / y [B, U] integer -> NHWC [B, H, W, C] map, per pixel summed in ascending unit index
+at::Tensor scatter_conn_fwd(const at::Tensor& proj, const at::Tensor& x, const at::Tensor& y, int64_t H, int64_t W) {
+  TORCH_CHECK(proj.dim() == 3 && H >= 1 && W >= 1 && H * W * proj.size(2) < (1LL << 31) && proj.size(0) < (1LL << 31),
+              "scatter_connection: proj [B, U, C]");
+  check_scatter_conn(proj, x, y, proj.size(0), proj.size(1));
+  c10::hip::HIPGuard g(proj.device().index());
+  auto out = at::empty({proj.size(0), H, W, proj.size(2)}, proj.options());
+  as::scatter_conn_fwd(proj.data_ptr(), dt(proj), x.data_ptr(), idx_dtype_code(x), y.data_ptr(), idx_dtype_code(y),
+                       out.data_ptr(), proj.size(0), static_cast<int>(proj.size(1)), static_cast<int>(proj.size(2)),
+                       static_cast<int>(H), static_cast<int>(W), stream());
+  return out;
+}
+
+// dout NHWC [B, H, W, C] -> dproj [B, U, C] = dout at each unit's pixel
+at::Tensor scatter_conn_bwd(const at::Tensor& dout, const at::Tensor& x, const at::Tensor& y, int64_t U) {
+  TORCH_CHECK(dout.dim() == 4, "scatter_connection: dout [B, H, W, C]");
+  check_scatter_conn(dout, x, y, dout.size(0), U);
+  c10::hip::HIPGuard g(dout.device().index());
+  auto dproj = at::empty({dout.size(0), U, dout.size(3)}, dout.options());
+  as::scatter_conn_bwd(dout.data_ptr(), dt(dout), x.data_ptr(), idx_dtype_code(x), y.data_ptr(), idx_dtype_code(y),
+                       dproj.data_ptr(), dout.size(0), static_cast<int>(U), static_cast<int>(dout.size(3)),
+                       static_cast<int>(dout.size(1)), static_cast<int>(dout.size(2)), stream());
+  return dproj;
 }
 
 // ---------------------------------------------------------------- location-head input (locin.hip)
@@ -2365,7 +2456,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none(), py::arg("res") = py::none(), py::arg("act") = 0, py::arg("variant") = 0);
   m.def("entity_pack", &entity_pack);
   m.def("embed_relu_fwd", &embed_relu_fwd);
-  m.def("embed_relu_bwd", &embed_relu_bwd);
+  m.def("embed_relu_bwd", &embed_relu_bwd, py::arg("dout"), py::arg("out"), py::arg("idx"), py::arg("V"),
+        py::arg("ordered") = false);
   m.def("gated_residual_fwd", &gated_residual_fwd, py::arg("y"), py::arg("g"), py::arg("sp"), py::arg("x"),
         py::arg("post") = py::none());
   m.def("gated_residual_bwd", &gated_residual_bwd, py::arg("dout"), py::arg("y"), py::arg("g"), py::arg("sp"),
@@ -2380,7 +2472,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("upsample2x_bwd", &upsample2x_bwd, py::arg("dy"), py::arg("mask") = py::none());
   m.def("entity_embed_wgrad", &entity_embed_wgrad);
   m.def("mm_k32", &mm_k32);
-  m.def("spatial_embed_fwd", &spatial_embed_fwd);
+  m.def("spatial_embed_fwd", &spatial_embed_fwd, py::arg("planes"), py::arg("effects"), py::arg("w_dense"),
+        py::arg("bias"), py::arg("rows"), py::arg("ex"), py::arg("ey"), py::arg("entity_num"), py::arg("out_dtype"),
+        py::arg("ordered") = false);
   m.def("spatial_gather_rows", &spatial_gather_rows, py::arg("dpre"), py::arg("ex"), py::arg("ey"),
         py::arg("entity_num"), py::arg("N"), py::arg("gate") = py::none());
   m.def("spatial_dense_input", &spatial_dense_input);
@@ -2420,13 +2514,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool2_bwd", &maxpool2_bwd, py::arg("dy"), py::arg("pos"), py::arg("H"), py::arg("W"),
         py::arg("mask") = py::none());
   m.def("maxpool2_bwd_relu", &maxpool2_bwd_relu);
-  m.def("spatial_embed_pool_fwd", &spatial_embed_pool_fwd);
+  m.def("spatial_embed_pool_fwd", &spatial_embed_pool_fwd, py::arg("planes"), py::arg("effects"), py::arg("w_dense"),
+        py::arg("bias"), py::arg("rows"), py::arg("ex"), py::arg("ey"), py::arg("entity_num"),
+        py::arg("ordered") = false);
   m.def("spatial_pool_supported", [](int64_t h, int64_t w) { return as::spatial_pool_supported(static_cast<int>(h), static_cast<int>(w)); });
   m.def("segment_sum", &segment_sum);
   m.def("spatial_dense_wgrad_pooled", &spatial_dense_wgrad_pooled);
   m.def("spatial_gather_rows_pooled", &spatial_gather_rows_pooled);
   m.def("entity_mean_pool", &entity_mean_pool);
-  m.def("table_grad", &table_grad);
+  m.def("table_grad", &table_grad, py::arg("src"), py::arg("idx"), py::arg("V"), py::arg("ordered") = false);
+  m.def("gather_steps_fwd", &gather_steps_fwd);
+  m.def("gather_steps_bwd", &gather_steps_bwd);
+  m.def("scatter_conn_fwd", &scatter_conn_fwd);
+  m.def("scatter_conn_bwd", &scatter_conn_bwd);
   m.def("conv3x3_fwd", &conv3x3_fwd);
   m.def("wgrad", &wgrad, py::arg("dy"), py::arg("x"), py::arg("cin"), py::arg("want_bias"),
         py::arg("bf16_out") = false);
@@ -2439,7 +2539,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("multi_strided_copy", &multi_strided_copy);
   m.def("loc_in_fwd", &loc_in_fwd);
   m.def("vsp_fwd", &vsp_fwd);
-  m.def("rl_loss", &rl_loss);
+  m.def("rl_loss", &rl_loss, py::arg("alp"), py::arg("blp"), py::arg("hm"), py::arg("ent"), py::arg("kl"), py::arg("v"),
+        py::arg("r"), py::arg("wm"), py::arg("atflag"), py::arg("sc"), py::arg("upgo_f"), py::arg("only_value"),
+        py::arg("ordered") = false);
   m.def("gate_chain", &gate_chain);
   m.def("gate_chain_f32", &gate_chain_f32);
   m.def("vsp_pool_fwd", &vsp_pool_fwd);
@@ -2453,7 +2555,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resmlp_fwd", &resmlp_fwd);
   m.def("resmlp_bwd", &resmlp_bwd);
   m.def("bo_encoder_fwd", &bo_encoder_fwd);
-  m.def("bo_encoder_bwd", &bo_encoder_bwd);
+  m.def("bo_encoder_bwd", &bo_encoder_bwd, py::arg("bo"), py::arg("loc"), py::arg("params"), py::arg("save"),
+        py::arg("dmean"), py::arg("ordered") = false);
   m.def("head_stats_bwd", &head_stats_bwd);
   m.def("act_grad_nhwc", &act_grad_nhwc);
   m.def("conv3x3_supported", [](int64_t cin, int64_t cout) { return as::conv3x3_supported(static_cast<int>(cin), static_cast<int>(cout)); });

@@ -144,13 +144,13 @@ void relu_cast(const float* x, void* y, int dt, long n, hipStream_t s);
 // fused: out [B,H,W,32] = relu(bias + Wd . dense(pixel) + sum of the rows of entities at the pixel)
 void spatial_embed_fused(const SpatialPlanes& sp, const float* wd, const float* bias, const void* rows, int rows_dt,
                          const uint8_t* ex, const uint8_t* ey, const int64_t* entity_num, void* out, int out_dt, int B,
-                         int N, int H, int W, int L, hipStream_t s);
+                         int N, int H, int W, int L, hipStream_t s, bool ordered = false);
 // pooled: relu(embed) -> max_pool2x2 in one pass (pixel-row pairs per workgroup); pooled [B,H/2,W/2,32] bf16,
 // pos [B,H/2,W/2,32] argmax bytes (maxpool2 format); needs spatial_pool_supported(H, W)
 bool spatial_pool_supported(int H, int W);
 void spatial_embed_pool(const SpatialPlanes& sp, const float* wd, const float* bias, const void* rows, const uint8_t* ex,
                         const uint8_t* ey, const int64_t* entity_num, void* pooled, uint8_t* pos, int B, int N, int H,
-                        int W, int L, hipStream_t s, bool f32 = false);
+                        int W, int L, hipStream_t s, bool f32 = false, bool ordered = false);
 // per-workgroup partial rows [spatial_wgrad_blocks(B)][32*24 + 32] of dWd (n-major) and db from dpre [B*H*W, 32]
 int spatial_wgrad_blocks(int B);
 void spatial_dense_wgrad(const SpatialPlanes& sp, const void* dpre, const void* gate, int dt, float* part, int B, int H,
@@ -456,9 +456,10 @@ struct BoWeights {
 void bo_encoder_fwd(const void* bo, const void* loc, int idt, const BoWeights& w, int wdt, float* out, float* save,
                     long B, hipStream_t st);
 // grad [replicas, kBoGradSize] fp32 (zeroed by the caller; observation b adds into replica b % replicas)
-// += parameter gradients for dmean [B, 64]; the caller sums the replicas
+// += parameter gradients for dmean [B, 64]; the caller sums the replicas.  ordered: `replicas` workgroups, each walking
+// its observations in ascending order with plain read-modify-writes (no atomics)
 void bo_encoder_bwd(const void* bo, const void* loc, int idt, const BoWeights& w, int wdt, const float* save,
-                    const float* dmean, float* grad, long B, int replicas, hipStream_t st);
+                    const float* dmean, float* grad, long B, int replicas, hipStream_t st, bool ordered = false);
 
 // ---- gemm_k32.hip ------------------------------------------------------------------------------
 // out [R][N] = a [R][32] . W [32][N], bf16; wT = W^T [N][32] contiguous; N % 16 == 0
@@ -503,6 +504,30 @@ int rl_loss_max_tb();
 void rl_loss(const float* alp, const float* blp, const float* hm, const float* ent, const float* kl, const float* v,
              const float* r, const float* wm, const float* atflag, const float* sc, int F, int T, int B, int upgo_f,
              int only_value, float* dalp, float* dent, float* dkl, float* dv, float* info, hipStream_t s);
+// the same with every info sum taken in a fixed order (no LDS float atomics); the gradients are per element either way
+void rl_loss_ordered(const float* alp, const float* blp, const float* hm, const float* ent, const float* kl,
+                     const float* v, const float* r, const float* wm, const float* atflag, const float* sc, int F, int T,
+                     int B, int upgo_f, int only_value, float* dalp, float* dent, float* dkl, float* dv, float* info,
+                     hipStream_t s);
+
+// ---- ordered.hip: order-fixed sums of the deterministic mode (no float atomics; idt codes as embed_relu_fwd)
+// workgroups of table_grad_ordered for U rows (single: one workgroup, the result written outright)
+int table_grad_ordered_blocks(long U, bool single);
+// part [blocks][V * D] fp32 (blocks > 1: reduce with column_reduce; blocks == 1: part is the result).  out_mask
+// null: rows with idx outside [0, V) skipped; else idx clamped and src counted only where out_mask > 0
+void table_grad_ordered(const void* src, const void* out_mask, int dt, const void* idx, int idt, float* part, long U,
+                        int V, int D, int blocks, hipStream_t s);
+// out [B, S, C] = key [B, N1, C] rows labels [B, S] (clamped to [0, N1)); dkey = sums of dout in ascending step
+void gather_steps_fwd(const void* key, int dt, const int64_t* labels, void* out, long B, int N1, int S, int C,
+                      hipStream_t s);
+void gather_steps_bwd(const void* dout, int dt, const int64_t* labels, void* dkey, long B, int N1, int S, int C,
+                      hipStream_t s);
+int scatter_conn_max_units();
+// out [B, H, W, C] = per-pixel sums of proj [B, U, C] in ascending unit index (x / y clamped); dproj = gather of dout
+void scatter_conn_fwd(const void* proj, int dt, const void* x, int xdt, const void* y, int ydt, void* out, long B, int U,
+                      int C, int H, int W, hipStream_t s);
+void scatter_conn_bwd(const void* dout, int dt, const void* x, int xdt, const void* y, int ydt, void* dproj, long B,
+                      int U, int C, int H, int W, hipStream_t s);
 
 // ---- gate_chain.hip: four chained 128 x 128 pointwise layers, activation tile resident in LDS
 // layer L: out[L] = epilogue(in @ m[L]^T) with m[L] [128 out][128 in] bf16; epilogue: + bias[L] (fp32,

@@ -240,7 +240,15 @@ __device__ __forceinline__ void mm_nn(const float* dY, const void* W, float* dA,
 // columns k and k + K/2: consecutive lanes take consecutive k, so every atomic instruction covers contiguous
 // addresses (a 4 x 4 tile per lane spread each instruction over 16-B strides: the backward got slower) and the
 // dY quad is one broadcast 16-B LDS read; 3 LDS reads per 8 FMAs.
-template <int K, int N>
+// DET (the deterministic backward: one workgroup owns the replica and walks its observations in order): the cell ->
+// thread mapping is the same for every observation, so the adds are plain read-modify-writes by the cell's owner.
+template <bool DET>
+__device__ __forceinline__ void grad_add(float* p, float v) {
+  if constexpr (DET) *p += v;
+  else atomicAdd(p, v);
+}
+
+template <int K, int N, bool DET>
 __device__ __forceinline__ void mm_grad(const float* dY, const float* A, float* G, float* gb) {
   static_assert(N % 4 == 0 && K % 2 == 0, "row quads, column halves");
   constexpr int KH = K / 2;
@@ -262,14 +270,14 @@ __device__ __forceinline__ void mm_grad(const float* dY, const float* A, float* 
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      atomicAdd(G + (n + i) * K + k, acc[i][0]);
-      atomicAdd(G + (n + i) * K + k + KH, acc[i][1]);
+      grad_add<DET>(G + (n + i) * K + k, acc[i][0]);
+      grad_add<DET>(G + (n + i) * K + k + KH, acc[i][1]);
     }
   }
   for (int n = threadIdx.x; n < N; n += 256) {
     float acc = 0.f;
     for (int t = 0; t < L; ++t) acc += dY[t * N + n];
-    atomicAdd(gb + n, acc);
+    grad_add<DET>(gb + n, acc);
   }
 }
 
@@ -291,9 +299,11 @@ __device__ __forceinline__ void layer_norm64(const float* X, const float* g, con
   __syncthreads();
 }
 
-// dX[t] += LN backward of dU (through the affine): xhat = (X - mu) rs;  also the affine gradients
+// dX[t] += LN backward of dU (through the affine): xhat = (X - mu) rs;  also the affine gradients.  DET: the four
+// waves' partial sums go through `red` (>= 512 floats of free LDS) and wave 0 adds them in wave order.
+template <bool DET>
 __device__ __forceinline__ void layer_norm64_bwd(const float* X, const float* mu, const float* rs, const float* g,
-                                                 const float* dU, float* dX, float* gw, float* gb) {
+                                                 const float* dU, float* dX, float* gw, float* gb, float* red) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   float aw = 0.f, ab = 0.f;
   for (int t = w; t < L; t += 4) {
@@ -306,8 +316,18 @@ __device__ __forceinline__ void layer_norm64_bwd(const float* X, const float* mu
     const float m2 = wave_sum(gx * xh) * (1.f / D);
     dX[t * D + lane] += rs[t] * (gx - m1 - xh * m2);
   }
-  atomicAdd(gw + lane, aw);
-  atomicAdd(gb + lane, ab);
+  if constexpr (DET) {
+    red[w * 64 + lane] = aw;
+    red[256 + w * 64 + lane] = ab;
+    __syncthreads();
+    if (w == 0) {
+      gw[lane] += ((red[lane] + red[64 + lane]) + red[128 + lane]) + red[192 + lane];
+      gb[lane] += ((red[256 + lane] + red[320 + lane]) + red[384 + lane]) + red[448 + lane];
+    }
+  } else {
+    atomicAdd(gw + lane, aw);
+    atomicAdd(gb + lane, ab);
+  }
   __syncthreads();
 }
 
@@ -444,17 +464,12 @@ struct alignas(16) SmemB {
   float wb[HID * (D + 1)];
 };
 
-template <typename WT>
-__global__ __launch_bounds__(256) void bo_bwd_kernel(const void* __restrict__ bo, const void* __restrict__ loc, int idt,
-                                                     BoWeights wts, const float* __restrict__ save,
-                                                     const float* __restrict__ dmean, float* __restrict__ grad,
-                                                     long B, int replicas) {
-  __shared__ SmemB s;
-  const long b = blockIdx.x;
+// the backward of observation b, added into `grad` (one replica of the gradient buffer)
+template <typename WT, bool DET>
+__device__ __forceinline__ void bo_bwd_observation(SmemB& s, const void* __restrict__ bo, const void* __restrict__ loc,
+                                                   int idt, const BoWeights& wts, const float* __restrict__ save,
+                                                   const float* __restrict__ dmean, float* __restrict__ grad, long b) {
   const int tid = threadIdx.x;
-  // every observation adds to the same ~77 K parameter gradients: spread the fp32 atomics over
-  // `replicas` copies (reduced afterwards) so ~B / replicas workgroups, not all B, contend per address
-  grad += (b % replicas) * static_cast<long>(kBoGradSize);
   for (int i = tid; i < L * D; i += 256) s.dX[i] = dmean[b * D + (i % D)] * (1.f / L);
   WPre pf;                                   // the next mm_nn's weight, loaded one phase ahead (as the forward)
   prefetch_w<HID, D, WT>(wts.w2[NL - 1], pf);
@@ -466,7 +481,7 @@ __global__ __launch_bounds__(256) void bo_bwd_kernel(const void* __restrict__ bo
     for (int i = tid; i < L * D; i += 256) s.dT[i] = rec[R_H2 + i] > 0.f ? s.dX[i] : 0.f;   // dH2 (pre-act)
     for (int i = tid; i < L * HID; i += 256) s.A[i] = rec[R_H1 + i];
     __syncthreads();
-    mm_grad<HID, D>(s.dT, s.A, gl + G_W2, gl + G_B2);
+    mm_grad<HID, D, DET>(s.dT, s.A, gl + G_W2, gl + G_B2);
     mm_nn_stage<HID, D>(pf, s.wb);
     prefetch_w<D, HID, WT>(wts.w1[l], pf);
     mm_nn_compute<HID, D>(s.dT, s.dH, s.wb);
@@ -474,17 +489,18 @@ __global__ __launch_bounds__(256) void bo_bwd_kernel(const void* __restrict__ bo
     __syncthreads();
     for (int i = tid; i < L * D; i += 256) s.A[i] = rec[R_U2 + i];
     __syncthreads();
-    mm_grad<D, HID>(s.dH, s.A, gl + G_W1, gl + G_B1);
+    mm_grad<D, HID, DET>(s.dH, s.A, gl + G_W1, gl + G_B1);
     mm_nn_stage<D, HID>(pf, s.wb);
     prefetch_w<16, D, WT>(wts.wp[l], pf);
     mm_nn_compute<D, HID>(s.dH, s.dT, s.wb);                                                   // dU2
-    layer_norm64_bwd(rec + R_XMID, rec + R_MU2, rec + R_RS2, wts.ln2w[l], s.dT, s.dX, gl + G_LN2W, gl + G_LN2B);
+    layer_norm64_bwd<DET>(rec + R_XMID, rec + R_MU2, rec + R_RS2, wts.ln2w[l], s.dT, s.dX, gl + G_LN2W, gl + G_LN2B,
+                          s.wb);
     // ---- attention branch: xmid = xin + (softmax(q k^T / sqrt 8) v) Wp^T + bp
     for (int i = tid; i < L * 16; i += 256) s.A[i] = rec[R_O + i];
     for (int i = tid; i < L * QD; i += 256) s.QKV[i] = rec[R_QKV + i];
     for (int i = tid; i < NH * L * L; i += 256) s.P[i] = rec[R_P + i];
     __syncthreads();
-    mm_grad<16, D>(s.dX, s.A, gl + G_WP, gl + G_BP);
+    mm_grad<16, D, DET>(s.dX, s.A, gl + G_WP, gl + G_BP);
     mm_nn_stage<16, D>(pf, s.wb);
     prefetch_w<D, QD, WT>(wts.wqkv[l], pf);
     mm_nn_compute<16, D>(s.dX, s.dO, s.wb);
@@ -522,33 +538,108 @@ __global__ __launch_bounds__(256) void bo_bwd_kernel(const void* __restrict__ bo
     }
     for (int i = tid; i < L * D; i += 256) s.A[i] = rec[R_U1 + i];
     __syncthreads();
-    mm_grad<D, QD>(s.dQKV, s.A, gl + G_WQKV, gl + G_BQKV);
+    mm_grad<D, QD, DET>(s.dQKV, s.A, gl + G_WQKV, gl + G_BQKV);
     mm_nn_stage<D, QD>(pf, s.wb);
     if (l > 0) prefetch_w<HID, D, WT>(wts.w2[l - 1], pf);
     mm_nn_compute<D, QD>(s.dQKV, s.dT, s.wb);                                                  // dU1
-    layer_norm64_bwd(rec + R_XIN, rec + R_MU1, rec + R_RS1, wts.ln1w[l], s.dT, s.dX, gl + G_LN1W, gl + G_LN1B);
+    layer_norm64_bwd<DET>(rec + R_XIN, rec + R_MU1, rec + R_RS1, wts.ln1w[l], s.dT, s.dX, gl + G_LN1W, gl + G_LN1B,
+                          s.wb);
   }
   // ---- embedding: x0 = relu(pre); pre = b0 + sum of the selected W0 columns
   const float* rec0 = save + (b * NL) * REC;
-  for (int i = tid; i < L * D; i += 256) {
-    const int t = i / D, n = i - t * D;
-    if (!(rec0[R_XIN + i] > 0.f)) continue;
-    const float g = s.dX[i];
-    long a = ld_idx(bo, b * L + t, idt);
-    a = a < 0 ? 0 : (a > NACT - 1 ? NACT - 1 : a);
-    long p = ld_idx(loc, b * L + t, idt);
-    p = p < 0 ? 0 : p;
-    const int lx = static_cast<int>(p % 160);
-    int ly = static_cast<int>(p / 160);
-    ly = ly > 1023 ? 1023 : ly;
-    float* gw = grad + G_W0 + n * IN;
-    atomicAdd(grad + G_B0 + n, g);
-    atomicAdd(gw + a, g);
-    atomicAdd(gw + NACT + t, g);
-    for (int j = 0; j < 10; ++j) {
-      if ((lx >> (9 - j)) & 1) atomicAdd(gw + 194 + j, g);
-      if ((ly >> (9 - j)) & 1) atomicAdd(gw + 204 + j, g);
+  if constexpr (DET) {
+    // thread n owns row n of W0 and b0[n]: the tokens' terms are summed in token order in registers (tokens that
+    // repeat an action are summed by the first of them), then every touched cell takes one read-modify-write
+    if (tid < D) {
+      const int n = tid;
+      float g[L], sx[10] = {}, sy[10] = {}, sb = 0.f;
+      int act[L];
+#pragma unroll
+      for (int t = 0; t < L; ++t) {
+        g[t] = rec0[R_XIN + t * D + n] > 0.f ? s.dX[t * D + n] : 0.f;
+        long a = ld_idx(bo, b * L + t, idt);
+        act[t] = static_cast<int>(a < 0 ? 0 : (a > NACT - 1 ? NACT - 1 : a));
+        long p = ld_idx(loc, b * L + t, idt);
+        p = p < 0 ? 0 : p;
+        const int lx = static_cast<int>(p % 160);
+        int ly = static_cast<int>(p / 160);
+        ly = ly > 1023 ? 1023 : ly;
+        sb += g[t];
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+          sx[j] += ((lx >> (9 - j)) & 1) ? g[t] : 0.f;
+          sy[j] += ((ly >> (9 - j)) & 1) ? g[t] : 0.f;
+        }
+      }
+      float* gw = grad + G_W0 + n * IN;
+      grad[G_B0 + n] += sb;
+      float old[L];
+#pragma unroll
+      for (int t = 0; t < L; ++t) old[t] = gw[NACT + t];
+#pragma unroll
+      for (int t = 0; t < L; ++t) gw[NACT + t] = old[t] + g[t];
+#pragma unroll
+      for (int j = 0; j < 10; ++j) {
+        gw[194 + j] += sx[j];
+        gw[204 + j] += sy[j];
+      }
+      bool first[L];
+#pragma unroll
+      for (int t = 0; t < L; ++t) {
+        first[t] = true;
+#pragma unroll
+        for (int u = 0; u < L; ++u) {
+          if (u < t && act[u] == act[t]) first[t] = false;
+          if (u > t && act[u] == act[t]) g[t] += g[u];     // g[u] of a later token is still its own term
+        }
+        old[t] = first[t] ? gw[act[t]] : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < L; ++t)
+        if (first[t]) gw[act[t]] = old[t] + g[t];
     }
+    __syncthreads();   // s.dX is rewritten for the workgroup's next observation
+  } else {
+    for (int i = tid; i < L * D; i += 256) {
+      const int t = i / D, n = i - t * D;
+      if (!(rec0[R_XIN + i] > 0.f)) continue;
+      const float g = s.dX[i];
+      long a = ld_idx(bo, b * L + t, idt);
+      a = a < 0 ? 0 : (a > NACT - 1 ? NACT - 1 : a);
+      long p = ld_idx(loc, b * L + t, idt);
+      p = p < 0 ? 0 : p;
+      const int lx = static_cast<int>(p % 160);
+      int ly = static_cast<int>(p / 160);
+      ly = ly > 1023 ? 1023 : ly;
+      float* gw = grad + G_W0 + n * IN;
+      atomicAdd(grad + G_B0 + n, g);
+      atomicAdd(gw + a, g);
+      atomicAdd(gw + NACT + t, g);
+      for (int j = 0; j < 10; ++j) {
+        if ((lx >> (9 - j)) & 1) atomicAdd(gw + 194 + j, g);
+        if ((ly >> (9 - j)) & 1) atomicAdd(gw + 204 + j, g);
+      }
+    }
+  }
+}
+
+// default: one workgroup per observation b, fp32 atomics into replica b % replicas.  DET (deterministic mode): grid =
+// replicas; workgroup r walks the observations r, r + replicas, ... in ascending order and updates replica r with
+// plain read-modify-writes (every gradient cell has one owner thread, the same for every observation).
+template <typename WT, bool DET>
+__global__ __launch_bounds__(256) void bo_bwd_kernel(const void* __restrict__ bo, const void* __restrict__ loc, int idt,
+                                                     BoWeights wts, const float* __restrict__ save,
+                                                     const float* __restrict__ dmean, float* __restrict__ grad,
+                                                     long B, int replicas) {
+  __shared__ SmemB s;
+  // every observation adds to the same ~77 K parameter gradients: spread the fp32 atomics over
+  // `replicas` copies (reduced afterwards) so ~B / replicas workgroups, not all B, contend per address
+  grad += (blockIdx.x % replicas) * static_cast<long>(kBoGradSize);
+  if constexpr (DET) {
+    for (long b = blockIdx.x; b < B; b += replicas)
+      bo_bwd_observation<WT, true>(s, bo, loc, idt, wts, save, dmean, grad, b);
+  } else {
+    bo_bwd_observation<WT, false>(s, bo, loc, idt, wts, save, dmean, grad, blockIdx.x);
   }
 }
 
@@ -566,14 +657,21 @@ void bo_encoder_fwd(const void* bo, const void* loc, int idt, const BoWeights& w
 }
 
 void bo_encoder_bwd(const void* bo, const void* loc, int idt, const BoWeights& w, int wdt, const float* save,
-                    const float* dmean, float* grad, long B, int replicas, hipStream_t st) {
+                    const float* dmean, float* grad, long B, int replicas, hipStream_t st, bool ordered) {
   if (B == 0) return;
-  if (wdt == DT_BF16)
-    hipLaunchKernelGGL(bo_bwd_kernel<bf16_t>, dim3(static_cast<unsigned>(B)), dim3(256), 0, st, bo, loc, idt, w, save,
-                       dmean, grad, B, replicas);
+  const dim3 grid(static_cast<unsigned>(ordered ? replicas : B));
+  if (wdt == DT_BF16 && ordered)
+    hipLaunchKernelGGL((bo_bwd_kernel<bf16_t, true>), grid, dim3(256), 0, st, bo, loc, idt, w, save, dmean, grad, B,
+                       replicas);
+  else if (wdt == DT_BF16)
+    hipLaunchKernelGGL((bo_bwd_kernel<bf16_t, false>), grid, dim3(256), 0, st, bo, loc, idt, w, save, dmean, grad, B,
+                       replicas);
+  else if (ordered)
+    hipLaunchKernelGGL((bo_bwd_kernel<float, true>), grid, dim3(256), 0, st, bo, loc, idt, w, save, dmean, grad, B,
+                       replicas);
   else
-    hipLaunchKernelGGL(bo_bwd_kernel<float>, dim3(static_cast<unsigned>(B)), dim3(256), 0, st, bo, loc, idt, w, save,
-                       dmean, grad, B, replicas);
+    hipLaunchKernelGGL((bo_bwd_kernel<float, false>), grid, dim3(256), 0, st, bo, loc, idt, w, save, dmean, grad, B,
+                       replicas);
 }
 
 }  // namespace as

@@ -25,6 +25,9 @@ constexpr int kMaxTB = 2048;   // G_upgo staging in LDS
 
 __device__ __forceinline__ void lds_add(float* p, float v) { atomicAdd(p, v); }
 
+// DET (the deterministic mode): every sum that lds_add takes in arrival order is taken in a fixed order instead -
+// each lane stages its terms in LDS and one fixed thread per quantity adds them in lane order.
+template <bool DET>
 __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict__ alp, const float* __restrict__ blp,
                                                          const float* __restrict__ hm, const float* __restrict__ ent,
                                                          const float* __restrict__ kl, const float* __restrict__ v,
@@ -48,6 +51,7 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
   __shared__ float g_up[kMaxTB];
   // accumulators: pg[f][h], td[f], rew[f], val[f], upgo[h], ent[h], kl[h], atkl
   __shared__ float s_pg[kMaxF][kH], s_td[kMaxF], s_rew[kMaxF], s_val[kMaxF], s_up[kH], s_ent[kH], s_kl[kH], s_at;
+  __shared__ float stage[DET ? 2 * kH + 1 : 1][kLossT];   // per-lane terms of the ordered sums
   const int tid = threadIdx.x;
   if (tid < kMaxF * kH) s_pg[tid / kH][tid % kH] = 0.f;
   if (tid < kMaxF) { s_td[tid] = 0.f; s_rew[tid] = 0.f; s_val[tid] = 0.f; }
@@ -56,38 +60,58 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
   __syncthreads();
 
   // ---- phase A: one lane per (field, column): TD(lambda = 0.8) critic returns, loss and dV; UPGO returns
-  for (int i = tid; i < F * B; i += kLossT) {
-    const int f = i / B, b = i % B;
-    const float* vf = v + static_cast<long>(f) * (T + 1) * B;
-    const float* rf = r + static_cast<long>(f) * TB;
-    const float* wf = wm + static_cast<long>(f) * TB;
-    float* dvf = dv + static_cast<long>(f) * (T + 1) * B;
-    const float gb = fsc[4 * f + 3], wbase = fsc[4 * f + 1];
-    float g = 0.f, td = 0.f, rs = 0.f, vs = vf[T * B + b];
-    dvf[T * B + b] = 0.f;
-    for (int t = T - 1; t >= 0; --t) {
-      const float lam = t == T - 1 ? 0.f : 0.8f;
-      const float rr = rf[t * B + b], vn = vf[(t + 1) * B + b], vc = vf[t * B + b], w = wf[t * B + b];
-      g = rr + gb * lam * g + gb * (1.f - lam) * vn;
-      const float e = g - vc;
-      td += 0.5f * e * e * w;
-      dvf[t * B + b] = -wbase * e * w * inv;
-      rs += rr;
-      vs += vc;
-    }
-    lds_add(&s_td[f], td);
-    lds_add(&s_rew[f], rs);
-    lds_add(&s_val[f], vs);
-    if (f == upgo_f) {
-      // upgo lambda[t] = [r[t+1] + V[t+2] >= V[t+1]] (1 at the last step, then forced 0 there), gamma 1
-      float gu = 0.f;
+  for (int base = 0; base < F * B; base += kLossT) {
+    const int i = base + tid;
+    const bool live = i < F * B;
+    const int f = live ? i / B : 0, b = live ? i % B : 0;
+    float td = 0.f, rs = 0.f, vs = 0.f;
+    if (live) {
+      const float* vf = v + static_cast<long>(f) * (T + 1) * B;
+      const float* rf = r + static_cast<long>(f) * TB;
+      const float* wf = wm + static_cast<long>(f) * TB;
+      float* dvf = dv + static_cast<long>(f) * (T + 1) * B;
+      const float gb = fsc[4 * f + 3], wbase = fsc[4 * f + 1];
+      float g = 0.f;
+      vs = vf[T * B + b];
+      dvf[T * B + b] = 0.f;
       for (int t = T - 1; t >= 0; --t) {
-        float lam = 1.f;
-        if (t + 1 < T) lam = (rf[(t + 1) * B + b] + vf[(t + 2) * B + b] >= vf[(t + 1) * B + b]) ? 1.f : 0.f;
-        if (t == T - 1) lam = 0.f;
-        gu = rf[t * B + b] + lam * gu + (1.f - lam) * vf[(t + 1) * B + b];
-        g_up[t * B + b] = gu;
+        const float lam = t == T - 1 ? 0.f : 0.8f;
+        const float rr = rf[t * B + b], vn = vf[(t + 1) * B + b], vc = vf[t * B + b], w = wf[t * B + b];
+        g = rr + gb * lam * g + gb * (1.f - lam) * vn;
+        const float e = g - vc;
+        td += 0.5f * e * e * w;
+        dvf[t * B + b] = -wbase * e * w * inv;
+        rs += rr;
+        vs += vc;
       }
+      if constexpr (!DET) {
+        lds_add(&s_td[f], td);
+        lds_add(&s_rew[f], rs);
+        lds_add(&s_val[f], vs);
+      }
+      if (f == upgo_f) {
+        // upgo lambda[t] = [r[t+1] + V[t+2] >= V[t+1]] (1 at the last step, then forced 0 there), gamma 1
+        float gu = 0.f;
+        for (int t = T - 1; t >= 0; --t) {
+          float lam = 1.f;
+          if (t + 1 < T) lam = (rf[(t + 1) * B + b] + vf[(t + 2) * B + b] >= vf[(t + 1) * B + b]) ? 1.f : 0.f;
+          if (t == T - 1) lam = 0.f;
+          gu = rf[t * B + b] + lam * gu + (1.f - lam) * vf[(t + 1) * B + b];
+          g_up[t * B + b] = gu;
+        }
+      }
+    }
+    if constexpr (DET) {
+      stage[0][tid] = td;
+      stage[1][tid] = rs;
+      stage[2][tid] = vs;
+      __syncthreads();
+      if (tid < 3) {
+        float* dst = tid == 0 ? s_td : (tid == 1 ? s_rew : s_val);
+        const int n = min(kLossT, F * B - base);
+        for (int l = 0; l < n; ++l) dst[(base + l) / B] += stage[tid][l];
+      }
+      __syncthreads();
     }
   }
   __syncthreads();
@@ -96,45 +120,61 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
   // (value pre-training: the sums still feed the info vector, the policy gradients are zero)
   const float gs = only_value ? 0.f : 1.f;
   {
-    for (int i = tid; i < kH * B; i += kLossT) {
-      const int h = i / B, b = i % B;
+    for (int base = 0; base < kH * B; base += kLossT) {
+      const int i = base + tid;
+      const bool live = i < kH * B;
+      const int h = live ? i / B : 0, b = live ? i % B : 0;
       const long hb = static_cast<long>(h) * TB;
       float up = 0.f;
-      for (int t = 0; t < T; ++t) dalp[hb + t * B + b] = 0.f;
-      for (int f = 0; f < F; ++f) {
-        // every field's V-trace sum is logged (pg/<field>), also at pg weight 0 (the reference config trains
-        // the policy on winloss only); the weight gates the gradient alone
-        const float wpg = fsc[4 * f];
-        const float gp = fsc[4 * f + 2];
-        const float* vf = v + static_cast<long>(f) * (T + 1) * B;
-        const float* rf = r + static_cast<long>(f) * TB;
-        const float* wf = wm + static_cast<long>(f) * TB;
-        float acc = 0.f, pg = 0.f;
-        for (int t = T - 1; t >= 0; --t) {
-          const int o = t * B + b;
-          const float rho = fminf(__expf(alp[hb + o] - blp[hb + o]), 1.f);
-          const float vn = vf[(t + 1) * B + b], vc = vf[o], rr = rf[o];
-          // vs_next = acc[t+1] + V[t+1] (t < T-1), V[T] at the last step
-          const float vs_next = (t == T - 1 ? 0.f : acc) + vn;
-          const float adv = rho * (rr + gp * vs_next - vc);
-          const float delta = rho * (rr + gp * vn - vc);
-          acc = gp * rho * acc + delta;
-          const float c = adv * hm[hb + o] * wf[o];
-          pg += -c * alp[hb + o];
-          dalp[hb + o] += -gs * wpg * pg_w[h] * c * inv;
+      if (live) {
+        for (int t = 0; t < T; ++t) dalp[hb + t * B + b] = 0.f;
+        for (int f = 0; f < F; ++f) {
+          // every field's V-trace sum is logged (pg/<field>), also at pg weight 0 (the reference config trains
+          // the policy on winloss only); the weight gates the gradient alone
+          const float wpg = fsc[4 * f];
+          const float gp = fsc[4 * f + 2];
+          const float* vf = v + static_cast<long>(f) * (T + 1) * B;
+          const float* rf = r + static_cast<long>(f) * TB;
+          const float* wf = wm + static_cast<long>(f) * TB;
+          float acc = 0.f, pg = 0.f;
+          for (int t = T - 1; t >= 0; --t) {
+            const int o = t * B + b;
+            const float rho = fminf(__expf(alp[hb + o] - blp[hb + o]), 1.f);
+            const float vn = vf[(t + 1) * B + b], vc = vf[o], rr = rf[o];
+            // vs_next = acc[t+1] + V[t+1] (t < T-1), V[T] at the last step
+            const float vs_next = (t == T - 1 ? 0.f : acc) + vn;
+            const float adv = rho * (rr + gp * vs_next - vc);
+            const float delta = rho * (rr + gp * vn - vc);
+            acc = gp * rho * acc + delta;
+            const float c = adv * hm[hb + o] * wf[o];
+            pg += -c * alp[hb + o];
+            dalp[hb + o] += -gs * wpg * pg_w[h] * c * inv;
+          }
+          if constexpr (DET) stage[f][tid] = pg;
+          else lds_add(&s_pg[f][h], pg);
         }
-        lds_add(&s_pg[f][h], pg);
+        if (upgo_f >= 0) {
+          const float* vf = v + static_cast<long>(upgo_f) * (T + 1) * B;
+          for (int t = 0; t < T; ++t) {
+            const int o = t * B + b;
+            const float rho = fminf(__expf(alp[hb + o] - blp[hb + o]), 1.f);
+            const float ua = rho * (g_up[o] - vf[o]) * hm[hb + o];
+            up += -ua * alp[hb + o];
+            dalp[hb + o] += -gs * w_upgo * upgo_w[h] * ua * inv;
+          }
+          if constexpr (!DET) lds_add(&s_up[h], up);
+        }
       }
-      if (upgo_f >= 0) {
-        const float* vf = v + static_cast<long>(upgo_f) * (T + 1) * B;
-        for (int t = 0; t < T; ++t) {
-          const int o = t * B + b;
-          const float rho = fminf(__expf(alp[hb + o] - blp[hb + o]), 1.f);
-          const float ua = rho * (g_up[o] - vf[o]) * hm[hb + o];
-          up += -ua * alp[hb + o];
-          dalp[hb + o] += -gs * w_upgo * upgo_w[h] * ua * inv;
+      if constexpr (DET) {
+        stage[kMaxF][tid] = up;
+        __syncthreads();
+        const int n = min(kLossT, kH * B - base);
+        if (tid < F) {
+          for (int l = 0; l < n; ++l) s_pg[tid][(base + l) / B] += stage[tid][l];
+        } else if (tid == kMaxF && upgo_f >= 0) {
+          for (int l = 0; l < n; ++l) s_up[(base + l) / B] += stage[kMaxF][l];
         }
-        lds_add(&s_up[h], up);
+        __syncthreads();
       }
     }
   }
@@ -160,14 +200,31 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
     dent[i] = only_value ? 0.f : -w_ent * ent_w[h] * m * inv;
     dkl[i] = dk;
   }
+  if constexpr (DET) {
 #pragma unroll
-  for (int h = 0; h < kH; ++h) {
-    const float se = wave_sum(pe[h]), sk = wave_sum(pk[h]);
-    if ((tid & 63) == 0) { lds_add(&s_ent[h], se); lds_add(&s_kl[h], sk); }
-  }
-  {
-    const float sa = wave_sum(pa);
-    if ((tid & 63) == 0) lds_add(&s_at, sa);
+    for (int h = 0; h < kH; ++h) {
+      stage[h][tid] = pe[h];
+      stage[kH + h][tid] = pk[h];
+    }
+    stage[2 * kH][tid] = pa;
+    __syncthreads();
+    if (tid < 2 * kH + 1) {
+      float a = 0.f;
+      for (int l = 0; l < kLossT; ++l) a += stage[tid][l];
+      if (tid < kH) s_ent[tid] = a;
+      else if (tid < 2 * kH) s_kl[tid - kH] = a;
+      else s_at = a;
+    }
+  } else {
+#pragma unroll
+    for (int h = 0; h < kH; ++h) {
+      const float se = wave_sum(pe[h]), sk = wave_sum(pk[h]);
+      if ((tid & 63) == 0) { lds_add(&s_ent[h], se); lds_add(&s_kl[h], sk); }
+    }
+    {
+      const float sa = wave_sum(pa);
+      if ((tid & 63) == 0) lds_add(&s_at, sa);
+    }
   }
   __syncthreads();
 
@@ -221,8 +278,16 @@ int rl_loss_max_tb() { return kMaxTB; }
 void rl_loss(const float* alp, const float* blp, const float* hm, const float* ent, const float* kl, const float* v,
              const float* r, const float* wm, const float* atflag, const float* sc, int F, int T, int B, int upgo_f,
              int only_value, float* dalp, float* dent, float* dkl, float* dv, float* info, hipStream_t s) {
-  hipLaunchKernelGGL(rl_loss_kernel, dim3(1), dim3(kLossT), 0, s, alp, blp, hm, ent, kl, v, r, wm, atflag, sc, F, T, B,
-                     upgo_f, only_value, dalp, dent, dkl, dv, info);
+  hipLaunchKernelGGL(rl_loss_kernel<false>, dim3(1), dim3(kLossT), 0, s, alp, blp, hm, ent, kl, v, r, wm, atflag, sc, F,
+                     T, B, upgo_f, only_value, dalp, dent, dkl, dv, info);
+}
+
+void rl_loss_ordered(const float* alp, const float* blp, const float* hm, const float* ent, const float* kl,
+                     const float* v, const float* r, const float* wm, const float* atflag, const float* sc, int F, int T,
+                     int B, int upgo_f, int only_value, float* dalp, float* dent, float* dkl, float* dv, float* info,
+                     hipStream_t s) {
+  hipLaunchKernelGGL(rl_loss_kernel<true>, dim3(1), dim3(kLossT), 0, s, alp, blp, hm, ent, kl, v, r, wm, atflag, sc, F,
+                     T, B, upgo_f, only_value, dalp, dent, dkl, dv, info);
 }
 
 }  // namespace as

@@ -449,7 +449,48 @@ __global__ __launch_bounds__(256) void spatial_dense_input_kernel(SpatialPlanes 
 // (one fp32 [npix, 32] round trip, 128-B strided stores per thread) + scatter_add_rows + relu_cast.
 constexpr int kSpTile = 256;
 
-template <typename TR, typename TO>
+// Deterministic mode (DET kernels below): the rows of observation b's entities inside the tile [p0, p0 + np) are
+// added to the LDS tile in ascending entity index, with no float atomic.  The entities are taken in rounds of 256;
+// a round's members are compacted into ent_list in entity order (wave ballot + the waves' counts), then the fixed
+// owner thread of (pixel class p & 7, channel c) walks the list and adds the entries of its class, so every
+// acc[p][c] has one writer and one order.  Call with acc complete and a barrier behind it; ends with a barrier.
+template <typename TR>
+__device__ __forceinline__ void add_entities_ordered(float (*acc)[33], int2* ent_list, const TR* __restrict__ rows,
+                                                     const uint8_t* __restrict__ ex, const uint8_t* __restrict__ ey,
+                                                     int b, int N, int ne, int H, int W, int p0, int np) {
+  __shared__ int wave_cnt[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = tid >> 5, c = tid & 31;
+  for (int base = 0; base < ne; base += kSpTile) {
+    const int n = base + tid;
+    int p = -1;
+    if (n < ne) {
+      const long bn = static_cast<long>(b) * N + n;
+      int x = ex[bn], y = ey[bn];
+      x = x < W ? x : W - 1;
+      y = y < H ? y : H - 1;
+      p = y * W + x - p0;
+    }
+    const bool inside = p >= 0 && p < np;
+    const unsigned long long m = __ballot(inside);
+    if (lane == 0) wave_cnt[w] = __popcll(m);
+    __syncthreads();
+    int slot = __popcll(m & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      slot += k < w ? wave_cnt[k] : 0;
+      total += wave_cnt[k];
+    }
+    if (inside) ent_list[slot] = make_int2(n, p);
+    __syncthreads();
+    for (int j = 0; j < total; ++j) {
+      const int2 e = ent_list[j];
+      if ((e.y & 7) == g) acc[e.y][c] += Cvt<TR>::load(rows, (static_cast<long>(b) * N + e.x) * 32 + c);
+    }
+    __syncthreads();
+  }
+}
+
+template <typename TR, typename TO, bool DET>
 __global__ __launch_bounds__(256) void spatial_embed_fused_kernel(SpatialPlanes sp, const float* __restrict__ wd,
                                                                   const float* __restrict__ bias,
                                                                   const TR* __restrict__ rows,
@@ -511,30 +552,34 @@ __global__ __launch_bounds__(256) void spatial_embed_fused_kernel(SpatialPlanes 
   // entities of this observation inside the tile: one position test per entity (a compacted LDS list),
   // then the listed rows' 32 channels in parallel
   const int ne = static_cast<int>(entity_num[b] < N ? entity_num[b] : N);
-  for (int n = tid; n < ne; n += 256) {
-    const long bn = static_cast<long>(b) * N + n;
-    int x = ex[bn], y = ey[bn];
-    x = x < W ? x : W - 1;
-    y = y < H ? y : H - 1;
-    const int p = y * W + x - p0;
-    if (p >= 0 && p < np) {
-      const int slot = atomicAdd(&ent_cnt, 1);
-      if (slot < kSpTile) {
-        ent_list[slot] = make_int2(n, p);
-      } else {   // list full (> 256 entities in one tile): add this row directly
-        for (int c = 0; c < 32; ++c) atomicAdd(&acc[p][c], Cvt<TR>::load(rows, bn * 32 + c));
+  if constexpr (DET) {
+    add_entities_ordered<TR>(acc, ent_list, rows, ex, ey, b, N, ne, H, W, p0, np);
+  } else {
+    for (int n = tid; n < ne; n += 256) {
+      const long bn = static_cast<long>(b) * N + n;
+      int x = ex[bn], y = ey[bn];
+      x = x < W ? x : W - 1;
+      y = y < H ? y : H - 1;
+      const int p = y * W + x - p0;
+      if (p >= 0 && p < np) {
+        const int slot = atomicAdd(&ent_cnt, 1);
+        if (slot < kSpTile) {
+          ent_list[slot] = make_int2(n, p);
+        } else {   // list full (> 256 entities in one tile): add this row directly
+          for (int c = 0; c < 32; ++c) atomicAdd(&acc[p][c], Cvt<TR>::load(rows, bn * 32 + c));
+        }
       }
     }
+    __syncthreads();
+    const int nl = ent_cnt < kSpTile ? ent_cnt : kSpTile;
+    for (int i = tid; i < nl * 32; i += 256) {
+      const int c = i & 31;
+      const int2 e = ent_list[i >> 5];
+      const long bn = static_cast<long>(b) * N + e.x;
+      atomicAdd(&acc[e.y][c], Cvt<TR>::load(rows, bn * 32 + c));
+    }
+    __syncthreads();
   }
-  __syncthreads();
-  const int nl = ent_cnt < kSpTile ? ent_cnt : kSpTile;
-  for (int i = tid; i < nl * 32; i += 256) {
-    const int c = i & 31;
-    const int2 e = ent_list[i >> 5];
-    const long bn = static_cast<long>(b) * N + e.x;
-    atomicAdd(&acc[e.y][c], Cvt<TR>::load(rows, bn * 32 + c));
-  }
-  __syncthreads();
   const long o0 = (static_cast<long>(b) * HW + p0) * 32;
   for (int i = tid; i < np * 32; i += 256) {
     const int p = i >> 5, c = i & 31;
@@ -667,6 +712,7 @@ __device__ __forceinline__ void mark_effects(const SpatialPlanes& sp, uint32_t* 
   }
 }
 
+template <bool DET>
 __global__ __launch_bounds__(256) void spatial_embed_mfma_kernel(SpatialPlanes sp, const float* __restrict__ wd,
                                                                  const float* __restrict__ bias,
                                                                  const bf16_t* __restrict__ rows,
@@ -742,30 +788,34 @@ __global__ __launch_bounds__(256) void spatial_embed_mfma_kernel(SpatialPlanes s
   // entities of this observation inside the tile: one position test per entity (a compacted LDS list),
   // then the listed rows' 32 channels in parallel
   const int ne = static_cast<int>(entity_num[b] < N ? entity_num[b] : N);
-  for (int n = tid; n < ne; n += 256) {
-    const long bn = static_cast<long>(b) * N + n;
-    int x = ex[bn], y = ey[bn];
-    x = x < W ? x : W - 1;
-    y = y < H ? y : H - 1;
-    const int p = y * W + x - p0;
-    if (p >= 0 && p < np) {
-      const int slot = atomicAdd(&ent_cnt, 1);
-      if (slot < kSpTile) {
-        ent_list[slot] = make_int2(n, p);
-      } else {   // list full (> 256 entities in one tile): add this row directly
-        for (int c = 0; c < 32; ++c) atomicAdd(&acc_s[p][c], bf2f(rows[bn * 32 + c]));
+  if constexpr (DET) {
+    add_entities_ordered<bf16_t>(acc_s, ent_list, rows, ex, ey, b, N, ne, H, W, p0, np);
+  } else {
+    for (int n = tid; n < ne; n += 256) {
+      const long bn = static_cast<long>(b) * N + n;
+      int x = ex[bn], y = ey[bn];
+      x = x < W ? x : W - 1;
+      y = y < H ? y : H - 1;
+      const int p = y * W + x - p0;
+      if (p >= 0 && p < np) {
+        const int slot = atomicAdd(&ent_cnt, 1);
+        if (slot < kSpTile) {
+          ent_list[slot] = make_int2(n, p);
+        } else {   // list full (> 256 entities in one tile): add this row directly
+          for (int c = 0; c < 32; ++c) atomicAdd(&acc_s[p][c], bf2f(rows[bn * 32 + c]));
+        }
       }
     }
+    __syncthreads();
+    const int nl = ent_cnt < kSpTile ? ent_cnt : kSpTile;
+    for (int i = tid; i < nl * 32; i += 256) {
+      const int c = i & 31;
+      const int2 e = ent_list[i >> 5];
+      const long bn = static_cast<long>(b) * N + e.x;
+      atomicAdd(&acc_s[e.y][c], bf2f(rows[bn * 32 + c]));
+    }
+    __syncthreads();
   }
-  __syncthreads();
-  const int nl = ent_cnt < kSpTile ? ent_cnt : kSpTile;
-  for (int i = tid; i < nl * 32; i += 256) {
-    const int c = i & 31;
-    const int2 e = ent_list[i >> 5];
-    const long bn = static_cast<long>(b) * N + e.x;
-    atomicAdd(&acc_s[e.y][c], bf2f(rows[bn * 32 + c]));
-  }
-  __syncthreads();
   // relu + bf16, 8 channels (16 B) per store
   uint4* o = reinterpret_cast<uint4*>(out + (static_cast<long>(b) * HW + p0) * 32);
   for (int i = tid; i < np * 4; i += 256) {
@@ -788,7 +838,7 @@ constexpr int kPoolMF = kPoolTile / 64;   // 16-pixel MFMA row fragments per wav
 // T = bf16_t: the mixed-precision step (W as hi + lo bf16, values compared as the bf16 map would hold them);
 // T = float: the fp32 step (W as three bf16 parts, ~fp32-exact products against the exact-in-bf16 planes; fp32
 // entity rows, fp32 pooled output)
-template <typename T>
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void spatial_embed_pool_kernel(SpatialPlanes sp, const float* __restrict__ wd,
                                                                  const float* __restrict__ bias,
                                                                  const T* __restrict__ rows,
@@ -876,30 +926,34 @@ __global__ __launch_bounds__(256) void spatial_embed_pool_kernel(SpatialPlanes s
   }
   __syncthreads();
   const int ne = static_cast<int>(entity_num[b] < N ? entity_num[b] : N);
-  for (int n = tid; n < ne; n += 256) {
-    const long bn = static_cast<long>(b) * N + n;
-    int x = ex[bn], y = ey[bn];
-    x = x < W ? x : W - 1;
-    y = y < H ? y : H - 1;
-    const int p = y * W + x - p0;
-    if (p >= 0 && p < np) {
-      const int slot = atomicAdd(&ent_cnt, 1);
-      if (slot < kSpTile) {
-        ent_list[slot] = make_int2(n, p);
-      } else {
-        for (int c = 0; c < 32; ++c) atomicAdd(&acc_s[p][c], Cvt<T>::load(rows, bn * 32 + c));
+  if constexpr (DET) {
+    add_entities_ordered<T>(acc_s, ent_list, rows, ex, ey, b, N, ne, H, W, p0, np);
+  } else {
+    for (int n = tid; n < ne; n += 256) {
+      const long bn = static_cast<long>(b) * N + n;
+      int x = ex[bn], y = ey[bn];
+      x = x < W ? x : W - 1;
+      y = y < H ? y : H - 1;
+      const int p = y * W + x - p0;
+      if (p >= 0 && p < np) {
+        const int slot = atomicAdd(&ent_cnt, 1);
+        if (slot < kSpTile) {
+          ent_list[slot] = make_int2(n, p);
+        } else {
+          for (int c = 0; c < 32; ++c) atomicAdd(&acc_s[p][c], Cvt<T>::load(rows, bn * 32 + c));
+        }
       }
     }
+    __syncthreads();
+    const int nl = ent_cnt < kSpTile ? ent_cnt : kSpTile;
+    for (int i = tid; i < nl * 32; i += 256) {
+      const int c = i & 31;
+      const int2 e = ent_list[i >> 5];
+      const long bn = static_cast<long>(b) * N + e.x;
+      atomicAdd(&acc_s[e.y][c], Cvt<T>::load(rows, bn * 32 + c));
+    }
+    __syncthreads();
   }
-  __syncthreads();
-  const int nl = ent_cnt < kSpTile ? ent_cnt : kSpTile;
-  for (int i = tid; i < nl * 32; i += 256) {
-    const int c = i & 31;
-    const int2 e = ent_list[i >> 5];
-    const long bn = static_cast<long>(b) * N + e.x;
-    atomicAdd(&acc_s[e.y][c], Cvt<T>::load(rows, bn * 32 + c));
-  }
-  __syncthreads();
   // relu + 2x2 max (first maximum in window order wins, NaN propagates: maxpool2_fwd's rule) -> 8 channels
   // of one pooled pixel per thread: 16-B value store + 8 argmax bytes
   const long obase = (static_cast<long>(b) * Ho + rp) * Wo;
@@ -1285,14 +1339,15 @@ bool spatial_pool_supported(int H, int W) { return H % 2 == 0 && W % 2 == 0 && 2
 
 void spatial_embed_pool(const SpatialPlanes& sp, const float* wd, const float* bias, const void* rows, const uint8_t* ex,
                         const uint8_t* ey, const int64_t* entity_num, void* pooled, uint8_t* pos, int B, int N, int H,
-                        int W, int L, hipStream_t s, bool f32) {
-  if (f32)
-    hipLaunchKernelGGL(spatial_embed_pool_kernel<float>, dim3(B * (H / 2)), dim3(256), 0, s, sp, wd, bias,
-                       static_cast<const float*>(rows), ex, ey, entity_num, static_cast<float*>(pooled), pos, N, H, W, L);
-  else
-    hipLaunchKernelGGL(spatial_embed_pool_kernel<bf16_t>, dim3(B * (H / 2)), dim3(256), 0, s, sp, wd, bias,
-                       static_cast<const bf16_t*>(rows), ex, ey, entity_num, static_cast<bf16_t*>(pooled), pos, N, H, W,
-                       L);
+                        int W, int L, hipStream_t s, bool f32, bool ordered) {
+#define AS_SPP(T, DET)                                                                                              \
+  hipLaunchKernelGGL((spatial_embed_pool_kernel<T, DET>), dim3(B * (H / 2)), dim3(256), 0, s, sp, wd, bias,          \
+                     static_cast<const T*>(rows), ex, ey, entity_num, static_cast<T*>(pooled), pos, N, H, W, L)
+  if (f32 && ordered) AS_SPP(float, true);
+  else if (f32) AS_SPP(float, false);
+  else if (ordered) AS_SPP(bf16_t, true);
+  else AS_SPP(bf16_t, false);
+#undef AS_SPP
 }
 
 void spatial_effect_bits(const SpatialPlanes& sp, uint8_t* bits, int B, int L, int HW, hipStream_t s) {
@@ -1343,16 +1398,25 @@ void gather_rows(const void* dpre, const void* gate, int dt, const uint8_t* ex, 
 
 void spatial_embed_fused(const SpatialPlanes& sp, const float* wd, const float* bias, const void* rows, int rows_dt,
                          const uint8_t* ex, const uint8_t* ey, const int64_t* entity_num, void* out, int out_dt, int B,
-                         int N, int H, int W, int L, hipStream_t s) {
+                         int N, int H, int W, int L, hipStream_t s, bool ordered) {
   const int tiles = (H * W + kSpTile - 1) / kSpTile;
   const dim3 grid(static_cast<unsigned>(B) * tiles);
   if (B == 0) return;
 #define AS_SP(TR, TO)                                                                                              \
-  hipLaunchKernelGGL((spatial_embed_fused_kernel<TR, TO>), grid, dim3(256), 0, s, sp, wd, bias,                    \
-                     static_cast<const TR*>(rows), ex, ey, entity_num, static_cast<TO*>(out), N, H, W, L, tiles)
-  if (rows_dt == DT_BF16 && out_dt == DT_BF16 && spatial_mfma())
-    hipLaunchKernelGGL(spatial_embed_mfma_kernel, grid, dim3(256), 0, s, sp, wd, bias, static_cast<const bf16_t*>(rows), ex,
-                       ey, entity_num, static_cast<bf16_t*>(out), N, H, W, L, tiles);
+  do {                                                                                                             \
+    if (ordered)                                                                                                   \
+      hipLaunchKernelGGL((spatial_embed_fused_kernel<TR, TO, true>), grid, dim3(256), 0, s, sp, wd, bias,          \
+                         static_cast<const TR*>(rows), ex, ey, entity_num, static_cast<TO*>(out), N, H, W, L, tiles); \
+    else                                                                                                           \
+      hipLaunchKernelGGL((spatial_embed_fused_kernel<TR, TO, false>), grid, dim3(256), 0, s, sp, wd, bias,         \
+                         static_cast<const TR*>(rows), ex, ey, entity_num, static_cast<TO*>(out), N, H, W, L, tiles); \
+  } while (0)
+  if (rows_dt == DT_BF16 && out_dt == DT_BF16 && spatial_mfma() && ordered)
+    hipLaunchKernelGGL(spatial_embed_mfma_kernel<true>, grid, dim3(256), 0, s, sp, wd, bias,
+                       static_cast<const bf16_t*>(rows), ex, ey, entity_num, static_cast<bf16_t*>(out), N, H, W, L, tiles);
+  else if (rows_dt == DT_BF16 && out_dt == DT_BF16 && spatial_mfma())
+    hipLaunchKernelGGL(spatial_embed_mfma_kernel<false>, grid, dim3(256), 0, s, sp, wd, bias,
+                       static_cast<const bf16_t*>(rows), ex, ey, entity_num, static_cast<bf16_t*>(out), N, H, W, L, tiles);
   else if (rows_dt == DT_BF16 && out_dt == DT_BF16) AS_SP(bf16_t, bf16_t);
   else if (rows_dt == DT_BF16) AS_SP(bf16_t, float);
   else if (out_dt == DT_BF16) AS_SP(float, bf16_t);

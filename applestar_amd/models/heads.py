@@ -96,7 +96,7 @@ class ActionTypeHead(nn.Module):
         # one-hot(a) @ W^T == column gather of action_map_fc1's weight (index_select: its backward is an
         # index_add of the 384 rows; advanced indexing's is a sort-based index_put, ~0.1 ms per table)
         w1 = self.action_map_fc1[0]
-        e1 = F.relu(w1.weight.t().index_select(0, action_type.long().reshape(-1)).view(*action_type.shape, -1)
+        e1 = F.relu(ops.index_rows(w1.weight.t(), action_type.long().reshape(-1)).view(*action_type.shape, -1)
                     + w1.bias)
         e1 = self.action_map_fc2(e1)
         embedding = self.glu1(e1, scalar_context) + self.glu2(lstm_output, scalar_context)
@@ -109,7 +109,7 @@ class ActionTypeHead(nn.Module):
 
     def teacher_embedding(self, lstm_output, scalar_context, action_type):
         w1 = self.action_map_fc1[0]
-        e1 = F.relu(w1.weight.t().index_select(0, action_type.long().reshape(-1)).view(*action_type.shape, -1)
+        e1 = F.relu(ops.index_rows(w1.weight.t(), action_type.long().reshape(-1)).view(*action_type.shape, -1)
                     + w1.bias)
         return self.glu1(self.action_map_fc2(e1), scalar_context) + self.glu2(lstm_output, scalar_context)
 
@@ -141,7 +141,7 @@ class _ArgMLPHead(nn.Module):
         if action is None:
             action = sample_from_logits(logits, u)
         w = self.embed_fc1[0]
-        e = F.relu(w.weight.t().index_select(0, action.long().reshape(-1)).view(*action.shape, -1) + w.bias)
+        e = F.relu(ops.index_rows(w.weight.t(), action.long().reshape(-1)).view(*action.shape, -1) + w.bias)
         return logits, action, embedding + self.embed_fc2(e)
 
     def teacher_logits(self, embedding, temperature: float = 1.0):
@@ -150,7 +150,7 @@ class _ArgMLPHead(nn.Module):
 
     def teacher_embedding(self, embedding, action):
         w = self.embed_fc1[0]
-        e = F.relu(w.weight.t().index_select(0, action.long().reshape(-1)).view(*action.shape, -1) + w.bias)
+        e = F.relu(ops.index_rows(w.weight.t(), action.long().reshape(-1)).view(*action.shape, -1) + w.bias)
         return embedding + self.embed_fc2(e)
 
 
@@ -242,7 +242,7 @@ class SelectedUnitsHead(nn.Module):
         if step_ok is not None:
             new = new & step_ok[None, :]
         if self.reduce_type == 'selected_units_num':
-            gathered = key.gather(1, labels.clamp(max=N1 - 1).unsqueeze(-1).expand(B, S, C))
+            gathered = ops.gather_steps(key, labels.clamp(max=N1 - 1))
             run_sum = torch.cumsum(gathered * new.unsqueeze(-1).to(gathered.dtype), 1)
             run_cnt = torch.cumsum(new.int(), 1)
             div = torch.where((selected_units_num != 0)[:, None], run_cnt.clamp(min=1), torch.ones_like(run_cnt))

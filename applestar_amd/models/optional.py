@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import ops
 from .blocks import FCBlock
 from .lstm import LNLSTMCell, StackedLNLSTM, _Layer
 
@@ -88,8 +89,8 @@ class AttentionPool(nn.Module):
         B, S = labels.shape
         C = key.shape[-1]
         s = self.scores(key)                                                         # [B,N,h]
-        gs = s.gather(1, labels.unsqueeze(-1).expand(B, S, self.head_num))           # [B,S,h]
-        gk = key.float().gather(1, labels.unsqueeze(-1).expand(B, S, C))             # [B,S,C]
+        gs = ops.gather_steps(s, labels)                                             # [B,S,h]
+        gk = ops.gather_steps(key.float(), labels)                                   # [B,S,C]
         newf = new.unsqueeze(-1)
         m = gs.masked_fill(~newf, float('-inf')).amax(1, keepdim=True)
         m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))

@@ -20,9 +20,11 @@ import torch.nn.functional as F
 
 from . import reference as ref
 from . import _ext
+from .native import set_deterministic, deterministic
 
 __all__ = ['linear', 'layer_norm', 'conv2d', 'max_pool2x2', 'segment_sum', 'gather_rows', 'embed_relu', 'gated_residual', 'lnlstm_layer', 'varlen_attention',
-           'masked_attention', 'scatter_connection', 'sequence_mask', 'native_enabled', 'set_native', 'upsample2x',
+           'masked_attention', 'scatter_connection', 'sequence_mask', 'native_enabled', 'set_native', 'set_deterministic',
+           'deterministic', 'gather_steps', 'index_rows', 'upsample2x',
            'upsample_conv_out', 'head_sample', 'target_unit_sample']
 
 _NATIVE_ENABLED = True
@@ -153,6 +155,15 @@ def gather_rows(table, idx):
     return table.index_select(0, idx)
 
 
+def index_rows(table, idx):
+    """table[idx] for a 2-D table: ``index_select`` (backward: torch's ``index_add_``, atomic on the GPU), or in
+    deterministic mode on the GPU the native gather whose backward sums in ascending position."""
+    n = _native(table)
+    if n is not None:
+        return n.index_rows(table, idx)
+    return table.index_select(0, idx)
+
+
 def gated_residual(y, g, sp, x):
     n = _native(x)
     if n is not None and n.has('gated_residual'):
@@ -199,7 +210,24 @@ def head_stats(logits, teacher, actions):
 
 
 def scatter_connection(proj, x, y, H: int, W: int):
+    """Sum the unit rows proj [B, N, C] into a [B, C, H, W] map.  GPU in deterministic mode: the native kernel that
+    adds each pixel's rows in ascending unit index; otherwise the torch index_add_ (atomics on the GPU)."""
+    if deterministic():
+        n = _native(proj)
+        if n is not None:
+            return n.scatter_connection(proj, x, y, H, W)
     return ref.scatter_connection(proj, x, y, H, W)
+
+
+def gather_steps(key, labels):
+    """key [B, N1, C], labels [B, S] in [0, N1) -> key rows [B, S, C].  GPU in deterministic mode: native gather whose
+    backward sums each key row's step gradients in ascending step; otherwise torch.gather (scatter_add backward)."""
+    if deterministic():
+        n = _native(key)
+        if n is not None:
+            return n.gather_steps(key, labels)
+    B, S = labels.shape
+    return key.gather(1, labels.long().unsqueeze(-1).expand(B, S, key.shape[-1]))
 
 
 def upsample2x(x):

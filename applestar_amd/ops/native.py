@@ -31,6 +31,23 @@ _IMPLEMENTED = {'entity_mean_pool', 'layer_norm', 'gated_residual', 'reverse_sca
                 'rl_loss', 'embed_relu', 'col_assemble', 'entity_pack', 'action_logp'}
 
 
+# Deterministic mode (docs/OPEN_ISSUES.md "Determinism"): the sites that sum with float atomics, or through torch's
+# index_add_ / scatter_add, take kernels whose summation order is a function of the operands alone.  Unlike the A/B
+# switches this flag is read at call time, so it can be toggled in-process.
+_DETERMINISTIC = os.environ.get('APPLESTAR_DETERMINISTIC', '0') == '1'
+
+
+def set_deterministic(flag: bool) -> bool:
+    """Turn the ordered (bit-reproducible) kernels on or off; returns the previous value."""
+    global _DETERMINISTIC
+    prev, _DETERMINISTIC = _DETERMINISTIC, bool(flag)
+    return prev
+
+
+def deterministic() -> bool:
+    return _DETERMINISTIC
+
+
 def has(name: str) -> bool:
     """True when this wrapper module implements ``name`` (the extension is loaded by ensure_loaded)."""
     return name in _IMPLEMENTED
@@ -362,7 +379,7 @@ class _SpatialEmbed(torch.autograd.Function):
         effects = list(tensors[n_planes:])
         _, out = _C.spatial_embed_fwd(planes, effects, _w32(w_dense),
                                       _w32(bias), rows.contiguous(), ex, ey, entity_num,
-                                      _dt_code(out_dtype))
+                                      _dt_code(out_dtype), _DETERMINISTIC)
         ctx.save_for_backward(out, ex, ey, entity_num, *tensors)
         ctx.n_planes = n_planes
         ctx.N = rows.shape[1]
@@ -420,7 +437,7 @@ class _SpatialEmbedPool(torch.autograd.Function):
         effects = list(tensors[n_planes:])
         pooled, pos = _C.spatial_embed_pool_fwd(planes, effects, _w32(w_dense),
                                                 _w32(bias), rows.contiguous(), ex, ey,
-                                                entity_num)
+                                                entity_num, _DETERMINISTIC)
         ctx.save_for_backward(pooled, pos, ex, ey, entity_num, *tensors)
         ctx.n_planes = n_planes
         ctx.N = rows.shape[1]
@@ -482,7 +499,7 @@ class _RLLossTail(torch.autograd.Function):
     def forward(ctx, alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value):
         c = lambda t: t.detach().float().contiguous()  # noqa: E731
         info, dalp, dent, dkl, dv = _C.rl_loss(c(alp), c(blp), c(hm), c(ent), c(kl), c(v), c(r), c(wm), c(atflag),
-                                               sc, int(upgo_f), bool(only_value))
+                                               sc, int(upgo_f), bool(only_value), _DETERMINISTIC)
         ctx.save_for_backward(dalp, dent, dkl, dv)
         ctx.dtypes = (alp.dtype, ent.dtype, kl.dtype, v.dtype)
         ctx.mark_non_differentiable(info)
@@ -685,14 +702,74 @@ class _GatherRows(torch.autograd.Function):
         d = dout.reshape(idx.numel(), -1)
         if d.dtype not in (torch.float32, torch.bfloat16):
             d = d.float()
-        return _C.table_grad(d.contiguous(), idx, ctx.V).to(ctx.dtype), None
+        return _C.table_grad(d.contiguous(), idx, ctx.V, _DETERMINISTIC).to(ctx.dtype), None
+
+
+def index_rows(table, idx):
+    """table[idx] (2-D table, 1-D idx) for a few hundred rows out of a table of any size.  Deterministic mode: the
+    native gather whose backward adds each table row's gradients in ascending position (``gather_steps`` on one
+    observation); otherwise ``index_select``, whose backward is torch's atomic ``index_add_``."""
+    if _DETERMINISTIC and table.dtype in (torch.float32, torch.bfloat16):
+        return gather_steps(table.unsqueeze(0), idx.reshape(1, -1))[0]
+    return table.index_select(0, idx)
 
 
 def gather_rows(table, idx):
     """table[idx] whose backward accumulates in LDS per block (tiny tables hit by ~1e5 indices)."""
     if table.shape[0] * table.shape[1] > 16384:
-        return table.index_select(0, idx)
+        return index_rows(table, idx)
     return _GatherRows.apply(table, idx.long().contiguous())
+
+
+# ---------------------------------------------------------------------------- ordered gather / scatter (ordered.hip)
+class _GatherSteps(torch.autograd.Function):
+    """key[b, labels[b, s], :] whose backward sums the step gradients of each key row in ascending step (ordered.hip):
+    the order-fixed form of ``key.gather(1, labels...)``, whose torch backward is a scatter_add."""
+
+    @staticmethod
+    def forward(ctx, key, labels):
+        ctx.save_for_backward(labels)
+        ctx.N1 = key.shape[1]
+        return _C.gather_steps_fwd(key.contiguous(), labels)
+
+    @staticmethod
+    def backward(ctx, dout):
+        labels, = ctx.saved_tensors
+        return _C.gather_steps_bwd(dout.contiguous(), labels, ctx.N1), None
+
+
+def gather_steps(key, labels):
+    """key [B, N1, C] (fp32 / bf16), labels [B, S] -> [B, S, C]; labels are clamped to [0, N1)."""
+    if key.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'gather_steps: fp32 / bf16 key expected, got {key.dtype}')
+    return _GatherSteps.apply(key, labels.long().contiguous())
+
+
+_INDEX_DTYPES = (torch.int64, torch.int32, torch.int16, torch.uint8, torch.int8)
+
+
+class _ScatterConnection(torch.autograd.Function):
+    """Per-pixel sums of the unit rows in ascending unit index (ordered.hip); backward is the plain gather."""
+
+    @staticmethod
+    def forward(ctx, proj, x, y, H, W):
+        ctx.save_for_backward(x, y)
+        ctx.U = proj.shape[1]
+        return from_nhwc(_C.scatter_conn_fwd(proj.contiguous(), x, y, H, W))
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, y = ctx.saved_tensors
+        return _C.scatter_conn_bwd(nhwc(dout), x, y, ctx.U), None, None, None, None
+
+
+def scatter_connection(proj, x, y, H: int, W: int):
+    """proj [B, U, C] (fp32 / bf16), x / y [B, U] integer coordinates (clamped like the reference) -> [B, C, H, W] as
+    an NHWC-contiguous view, each element summed in ascending unit index."""
+    if proj.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'scatter_connection: fp32 / bf16 rows expected, got {proj.dtype}')
+    x, y = (t.contiguous() if t.dtype in _INDEX_DTYPES else t.long().contiguous() for t in (x, y))
+    return _ScatterConnection.apply(proj, x, y, int(H), int(W))
 
 
 def entity_pack(entity_num, N: int, total: int):
@@ -776,7 +853,7 @@ class _EmbedRelu(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         idx, out = ctx.saved_tensors
-        return _C.embed_relu_bwd(dout.to(out.dtype).contiguous(), out, idx, ctx.V).to(ctx.dtype), None
+        return _C.embed_relu_bwd(dout.to(out.dtype).contiguous(), out, idx, ctx.V, _DETERMINISTIC).to(ctx.dtype), None
 
 
 def embed_relu(table, idx):
@@ -2441,7 +2518,7 @@ class _BOEncoder(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dmean):
         bo, loc, rec, *params = ctx.saved_tensors
-        flat = _C.bo_encoder_bwd(bo, loc, list(params), rec, dmean.float().contiguous())
+        flat = _C.bo_encoder_bwd(bo, loc, list(params), rec, dmean.float().contiguous(), _DETERMINISTIC)
         grads, srcs, off = [], [], 0
         for p in params:
             n = p.numel()

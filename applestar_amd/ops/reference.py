@@ -129,6 +129,37 @@ def scatter_connection(proj: torch.Tensor, x: torch.Tensor, y: torch.Tensor, H: 
     return out.view(B, H, W, C).permute(0, 3, 1, 2)
 
 
+def scatter_connection_ordered(proj: torch.Tensor, x: torch.Tensor, y: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """:func:`scatter_connection` with the summation order of the deterministic mode spelled out: each output element
+    is the fp32 sum of its units' rows in ascending unit index, starting from the first contribution; pixels with no
+    unit are +0.  A plain loop over the units (the observations and channels are independent); the bit-exact
+    oracle of the native ordered kernel."""
+    B, N, C = proj.shape
+    pix = y.long().clamp(0, H - 1) * W + x.long().clamp(0, W - 1)
+    rows = proj.float()
+    out = torch.zeros(B, H * W, C, dtype=torch.float32, device=proj.device)
+    seen = torch.zeros(B, H * W, dtype=torch.bool, device=proj.device)
+    ar = torch.arange(B, device=proj.device)
+    for u in range(N):
+        p = pix[:, u]
+        out[ar, p] = torch.where(seen[ar, p].unsqueeze(-1), out[ar, p] + rows[:, u], rows[:, u])
+        seen[ar, p] = True
+    return out.to(proj.dtype).view(B, H, W, C).permute(0, 3, 1, 2)
+
+
+def gather_steps_grad_ordered(dout: torch.Tensor, labels: torch.Tensor, N1: int) -> torch.Tensor:
+    """Gradient of ``key[b, labels[b, s], :]`` w.r.t. key [B, N1, C] in the deterministic mode's order: row n of
+    observation b is the fp32 sum of dout[b, s, :] over the steps with labels[b, s] == n in ascending s (zero for a
+    row no label names).  A plain loop over the steps; the bit-exact oracle of the native backward."""
+    B, S, C = dout.shape
+    lab = labels.long().clamp(0, N1 - 1)
+    dkey = torch.zeros(B, N1, C, dtype=torch.float32, device=dout.device)
+    ar = torch.arange(B, device=dout.device)
+    for s in range(S):
+        dkey[ar, lab[:, s]] = dkey[ar, lab[:, s]] + dout[:, s].float()
+    return dkey.to(dout.dtype)
+
+
 # ----------------------------------------------------------------------------- losses / RL math
 
 def categorical_stats(logits: torch.Tensor, actions: torch.Tensor):

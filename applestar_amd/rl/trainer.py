@@ -33,6 +33,9 @@ DEFAULT_LEARNER_CONFIG = AttrDict({
         # HIP-graph capture of the whole step (runtime/step_graph.py); GPU only.  It pays when the host, not the
         # GPU, is the bottleneck (the bf16 step; many ranks per node contending for CPU)
         'graph_step': False,
+        # ordered kernels at every summation site that has one (ops.set_deterministic; docs/OPEN_ISSUES.md
+        # 'Determinism'); can only turn the mode on, APPLESTAR_DETERMINISTIC=1 is never overridden
+        'deterministic': False,
     },
     'model': {'enable_baselines': ['winloss']},
 })

@@ -60,6 +60,10 @@ class TrainEngine:
     def _setup_engine(self, device):
         lc = self.cfg.learner
         self.device = torch.device(device)
+        if lc.get('deterministic', False):
+            # only ever on: a mode the environment (APPLESTAR_DETERMINISTIC=1) selected is never turned off here
+            from ..ops.native import set_deterministic
+            set_deterministic(True)
         self.model.to(self.device)
         if self.device.type == 'cuda':
             # MIOpen find-mode autotuning (cudnn.benchmark) is opt-in: it measured ~10% faster convs on the

@@ -26,6 +26,7 @@ DEFAULT_SL_CONFIG = AttrDict({
         'data': {'batch_size': 6, 'trajectory_length': 64},
         'bucket_mb': 32, 'comm_dtype': None,
         'amp_dtype': None,        # fp32 like the reference; 'bfloat16' = bf16 compute with fp32 masters
+        'deterministic': False,   # ordered kernels where they exist (ops.set_deterministic); only ever turns the mode on
     },
 })
 

@@ -4,13 +4,24 @@ the zero poison.  A deterministic forward that reads only what it wrote gives bi
 free memory held; any difference names a read of unwritten memory (the selected-units bf16 logit error moved from
 box to box).
 
-    python tools/diag/poison_probe.py [--precision bf16|fp32|both] [--backward]
+    python tools/diag/poison_probe.py [--precision bf16|fp32|both] [--backward] [--deterministic] [--bench-shape]
+
+``--bench-shape`` probes one batch of the bench configuration (6 x 64, up to 512 entities) instead of the four small
+ones.
+
+``--deterministic`` turns the deterministic mode on (``ops.set_deterministic``) for the probe - with ``--backward``
+every output and gradient is then expected to be identical - and first audits what is not ours: one full trainer
+step per precision at the bench configuration (6 x 64, up to 512 entities) under
+``torch.use_deterministic_algorithms(True, warn_only=True)``, listing every torch op it flags with its call site.
 """
 import argparse
+import collections
 import copy
 import math
 import os
 import sys
+import traceback
+import warnings
 
 import torch
 
@@ -68,15 +79,57 @@ def diff(a, b):
     return worst
 
 
+def torch_audit(precisions):
+    """One trainer step per precision at the bench shapes with torch's own determinism check in warn-only mode:
+    prints each flagged op (the warning text names it) with the innermost call sites inside this repository."""
+    root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    for prec in precisions:
+        tr = RLTrainer({'learner': {'use_value_feature': True, 'amp_dtype': 'bfloat16' if prec == 'bf16' else None},
+                        'model': {'enable_baselines': ['winloss']}}, device='cuda')
+        batch = to_device(rl_batch(6, 64, max_entities=512, seed=0), 'cuda')
+        tr.step(dict(batch))                                           # warm-up: one-off paths stay out of the list
+        flagged = collections.Counter()
+
+        def show(message, category, filename, lineno, file=None, line=None):
+            if 'deterministic' not in str(message):
+                return
+            stack = [f for f in traceback.extract_stack()[:-1]
+                     if f.filename.startswith(root) and 'poison_probe' not in f.filename]
+            site = ' <- '.join(f'{os.path.relpath(f.filename, root)}:{f.lineno}' for f in reversed(stack[-3:]))
+            flagged[(str(message).split('.')[0][:110], site or '(autograd engine: a backward node)')] += 1
+        torch.use_deterministic_algorithms(True, warn_only=True)
+        try:
+            with warnings.catch_warnings():                            # restores showwarning on exit
+                warnings.simplefilter('always')
+                warnings.showwarning = show
+                tr.step(dict(batch))
+                torch.cuda.synchronize()
+        finally:
+            torch.use_deterministic_algorithms(False)
+        print(f'[{prec}] torch.use_deterministic_algorithms(warn_only) over one bench-shape step: '
+              f'{len(flagged)} flagged site(s)', flush=True)
+        for (msg, site), n in flagged.most_common():
+            print(f'    {n:3d}x {msg}\n         at {site}', flush=True)
+        del tr, batch
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--precision', default='both')
     ap.add_argument('--backward', action='store_true')
+    ap.add_argument('--deterministic', action='store_true')
+    ap.add_argument('--bench-shape', action='store_true')
     args = ap.parse_args()
+    if args.deterministic:
+        from applestar_amd import ops
+        ops.set_deterministic(True)
+        torch_audit(['fp32', 'bf16'] if args.precision == 'both' else [args.precision])
     torch.manual_seed(0)
     cpu = Model({'learner': {'use_value_feature': True}, 'model': {'enable_baselines': ['winloss']}},
                 use_value_network=True)
-    batches = [rl_batch(2, 4, max_entities=48, seed=s) for s in (3, 0, 1, 2)]
+    batches = [rl_batch(6, 64, max_entities=512, seed=0)] if args.bench_shape else \
+        [rl_batch(2, 4, max_entities=48, seed=s) for s in (3, 0, 1, 2)]
     clean = True
     for prec in (['bf16', 'fp32'] if args.precision == 'both' else [args.precision]):
         cfg = {'learner': {'use_value_feature': True, 'amp_dtype': 'bfloat16' if prec == 'bf16' else None},
