@@ -387,6 +387,17 @@ void conv3x3_f32_v2(const float* x, const void* wsplit, const float* bias, const
                     int variant, hipStream_t s);
 void gemm_f32_v2(const float* a, const void* bsplit, const float* bias, const float* res, float* out, long M, int N,
                  int K, int act, int variant, hipStream_t s);
+// the same product with the input staged once per 16-channel chunk as a pre-split halo window (conv3x3_f32_halo.hip):
+// split mode, Cin % 16, Cout 32 / 64 / 128-multiples, W <= 80 (and the 32-bit bounds of conv3x3_f32_psb_supported).
+// conv_halo_f32_mode (APPLESTAR_CONV_HALO_F32): the output widths conv3x3_f32_psb sends there (bits: 1 = 32,
+// 2 = 64, 4 = 128-multiples; 0 = the ring kernel everywhere); _selected: supported and switched on for this width
+bool conv3x3_f32_halo_supported(int H, int W, int Cin, int Cout);
+bool conv3x3_f32_halo_selected(int H, int W, int Cin, int Cout);
+int conv_halo_f32_mode();
+void set_conv_halo_f32_mode(int mode);
+void conv3x3_f32_halo(const float* x, const void* wsplit, const float* bias, const float* res, const float* res2,
+                      long res2_rows, const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int act,
+                      hipStream_t s);
 
 // Strided multi-tensor copy (+ dtype conversion) into contiguous destinations: dst[t][i] for the dst index
 // i = ((i0 * size1 + i1) * size2 + i2) * size3 + i3 reads src[t][base + sum_k ik * stride_k] (strides may be

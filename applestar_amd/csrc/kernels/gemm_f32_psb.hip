@@ -387,6 +387,10 @@ int conv_v2_variant() {
 void conv3x3_f32_psb(const float* x, const void* wsplit, const float* bias, const float* res, const float* res2,
                      long res2_rows, const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int act,
                      hipStream_t s) {
+  if (conv3x3_f32_halo_selected(H, W, Cin, Cout)) {       // the halo-window kernel where it is switched on
+    conv3x3_f32_halo(x, wsplit, bias, res, res2, res2_rows, mask, out, B, H, W, Cin, Cout, act, s);
+    return;
+  }
   if (conv_v2_variant() >= 0) {
     conv3x3_f32_v2(x, wsplit, bias, res, res2, res2_rows, mask, out, B, H, W, Cin, Cout, act, conv_v2_variant(), s);
     return;

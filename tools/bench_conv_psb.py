@@ -1,7 +1,10 @@
 """The fp32 split-MFMA 3x3 conv on the ResBlock shape (19 x 20 x 128 -> 128, 390 observations): time per call,
 TF/s of fp32 products and max error against float64 (a row subsample), per kernel variant.
 
-    python tools/bench_conv_psb.py [iters] [variants...]      # variants: psb (shipped), v2 ... (experimental)
+    python tools/bench_conv_psb.py [iters] [variants...]      # variants: psb (ring), halo, v2 ... (experimental)
+
+The variants run in the order given, per shape, in this one process: ``psb halo psb halo psb halo`` alternates the
+ring and the halo-window kernel three times.
 
 Under ``rocprofv3 --pmc`` run with ITERS small: every launch is a dispatch in the counter table.
 """
@@ -33,14 +36,26 @@ def main():
                                          padding=1).permute(0, 2, 3, 1)
         flop = 2.0 * B * H * W * Ci * Co * 9
         for name in names:
-            if name == 'psb':
-                fn = lambda: C.conv3x3_f32_psb(x, ws, Co, bias, None, None, None, 1)   # noqa: E731
+            if name == 'psb':        # the shipped dispatch with the halo kernel switched off: the ring kernel
+                def fn():
+                    mode = C.conv_halo_f32_mode()
+                    C.set_conv_halo_f32_mode(0)
+                    out = C.conv3x3_f32_psb(x, ws, Co, bias, None, None, None, 1)
+                    C.set_conv_halo_f32_mode(mode)
+                    return out
+            elif name.startswith('halo'):     # conv3x3_f32_halo.hip; haloN: under conv_halo_f32_mode N
+                def fn(m=int(name[4:]) if name[4:].isdigit() else None):
+                    mode = C.conv_halo_f32_mode()
+                    C.set_conv_halo_f32_mode(mode if m is None else m)
+                    out = C.conv3x3_f32_halo(x, ws, Co, bias, None, None, None, 1)
+                    C.set_conv_halo_f32_mode(mode)
+                    return out
             else:
                 v = int(name[1:]) if name[1:].isdigit() else 0
                 fn = lambda v=v: C.conv3x3_f32_v2(x, ws, Co, bias, None, None, None, 1, v)      # noqa: E731
             out = fn()
             err = float((out[:4].double().cpu() - ref.relu()).abs().max() / ref.abs().max())
-            for _ in range(3):
+            for _ in range(10):
                 fn()
             torch.cuda.synchronize()
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
