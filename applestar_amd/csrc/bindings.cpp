@@ -1075,106 +1075,98 @@ std::vector<at::Tensor> multi_logp(const std::vector<at::Tensor>& logits, const 
 }
 
 // fp32 3 x 3 conv of NHWC x on the pre-split planes of a [Cout, 3, 3, Cin] weight (presplit_b of its [Cout, 9 Cin]
-// view): bias / res / act as conv3x3_f32, res2 (first rows) / mask as conv3x3_f32_epi2
+// view): bias / res / act as conv3x3_f32, res2 (first rows) / mask as conv3x3_f32_epi2.  Three entries with one
+// signature: conv3x3_f32_psb (the learner's: picks the kernel, conv3x3_f32_dispatch.hip) and one kernel design each
+// directly, conv3x3_f32_v2 (+ its variant) and conv3x3_f32_halo (whatever conv_halo_f32_mode selects).
+struct ConvPsbArgs {
+  at::Tensor out;                  // [B, H, W, Cout], allocated
+  const float* x;
+  const void* wsplit;
+  const float *bias, *res, *res2, *mask;      // nullptr: absent
+  long res2_rows;
+  int B, H, W, Cin, Cout;
+};
+
+typedef bool (*ConvPsbSupported)(int64_t M, int64_t H, int64_t W, int64_t Cin, int64_t Cout);
+
+static bool conv_psb_ok(int64_t M, int64_t, int64_t, int64_t Cin, int64_t Cout) {
+  return as::conv3x3_f32_psb_supported(M, static_cast<int>(Cin), static_cast<int>(Cout));
+}
+
+static bool conv_halo_ok(int64_t M, int64_t H, int64_t W, int64_t Cin, int64_t Cout) {
+  return conv_psb_ok(M, H, W, Cin, Cout) &&
+         as::conv3x3_f32_halo_supported(static_cast<int>(H), static_cast<int>(W), static_cast<int>(Cin),
+                                        static_cast<int>(Cout));
+}
+
+// validates the operands of entry `name` (the prefix of every message) and allocates out; `supported`: the entry's
+// shape predicate, `covers`: what it accepts, in words
+static ConvPsbArgs conv_psb_args(const std::string& name, ConvPsbSupported supported, const char* covers,
+                                 const at::Tensor& x, const at::Tensor& wsplit, int64_t Cout,
+                                 const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res,
+                                 const c10::optional<at::Tensor>& res2, const c10::optional<at::Tensor>& mask) {
+  TORCH_CHECK(x.is_cuda() && wsplit.is_cuda(), name, ": x / wsplit must be GPU tensors");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.dim() == 4 && x.is_contiguous(), name, ": contiguous NHWC fp32 x");
+  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), M = B * H * W;
+  TORCH_CHECK(supported(M, H, W, Cin, Cout), name, ": ", covers);
+  TORCH_CHECK(wsplit.scalar_type() == at::kByte && wsplit.is_contiguous() &&
+                  wsplit.numel() == as::presplit_b_bytes(static_cast<int>(Cout), static_cast<int>(9 * Cin)),
+              name, ": wsplit must be presplit_b of the [Cout, 9 Cin] weight");
+  // rows < 0: [Cout]; else whole rows of Cout, at most `rows` (exactly, if `all`)
+  auto fp = [&](const c10::optional<at::Tensor>& t, int64_t rows, bool all, const char* what) -> const float* {
+    if (!t || !t->defined()) return nullptr;
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->device() == x.device() &&
+                    (rows < 0 ? t->numel() == Cout : (t->numel() % Cout == 0 && t->numel() / Cout <= rows)) &&
+                    (!all || t->numel() == rows * Cout), name, ": ", what);
+    return t->data_ptr<float>();
+  };
+  ConvPsbArgs a;
+  a.x = x.data_ptr<float>();
+  a.wsplit = wsplit.data_ptr();
+  a.bias = fp(bias, -1, false, "bias [Cout]");
+  a.res = fp(res, M, true, "res [B, H, W, Cout]");
+  a.res2 = fp(res2, M, false, "res2 [b <= B, H, W, Cout]");
+  a.mask = fp(mask, M, true, "mask [B, H, W, Cout]");
+  a.res2_rows = a.res2 ? res2->numel() / Cout : 0;
+  a.B = static_cast<int>(B), a.H = static_cast<int>(H), a.W = static_cast<int>(W);
+  a.Cin = static_cast<int>(Cin), a.Cout = static_cast<int>(Cout);
+  a.out = at::empty({B, H, W, Cout}, x.options());
+  return a;
+}
+
 at::Tensor conv3x3_f32_psb(const at::Tensor& x, const at::Tensor& wsplit, int64_t Cout,
                            const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res,
                            const c10::optional<at::Tensor>& res2, const c10::optional<at::Tensor>& mask, int64_t act) {
-  check_cuda(x, "x");
-  check_cuda(wsplit, "wsplit");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.dim() == 4 && x.is_contiguous(), "conv3x3_f32_psb: NHWC fp32 x");
-  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), M = B * H * W;
-  TORCH_CHECK(as::conv3x3_f32_psb_supported(M, static_cast<int>(Cin), static_cast<int>(Cout)),
-              "conv3x3_f32_psb: Cout % 128, Cin % 16");
-  TORCH_CHECK(wsplit.scalar_type() == at::kByte && wsplit.is_contiguous() &&
-                  wsplit.numel() == as::presplit_b_bytes(static_cast<int>(Cout), static_cast<int>(9 * Cin)),
-              "conv3x3_f32_psb: wsplit must be presplit_b of the [Cout, 9 Cin] weight");
-  auto fp = [&](const c10::optional<at::Tensor>& t, int64_t rows, const char* what) -> const float* {
-    if (!t || !t->defined()) return nullptr;
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->device() == x.device() &&
-                    (rows < 0 ? t->numel() == Cout : (t->numel() % Cout == 0 && t->numel() / Cout <= rows)), what);
-    return t->data_ptr<float>();
-  };
-  const float* bp = fp(bias, -1, "conv3x3_f32_psb: bias [Cout]");
-  const float* rp = fp(res, M, "conv3x3_f32_psb: res [B, H, W, Cout]");
-  if (rp) TORCH_CHECK(res->numel() == M * Cout, "conv3x3_f32_psb: res [B, H, W, Cout]");
-  const float* r2 = fp(res2, M, "conv3x3_f32_psb: res2 [b <= B, H, W, Cout]");
-  const float* mk = fp(mask, M, "conv3x3_f32_psb: mask [B, H, W, Cout]");
-  if (mk) TORCH_CHECK(mask->numel() == M * Cout, "conv3x3_f32_psb: mask [B, H, W, Cout]");
+  const ConvPsbArgs a = conv_psb_args("conv3x3_f32_psb", conv_psb_ok, "Cout % 128 (64 / 32 on the ring), Cin % 16", x,
+                                      wsplit, Cout, bias, res, res2, mask);
   c10::hip::HIPGuard g(x.device().index());
-  auto out = at::empty({B, H, W, Cout}, x.options());
-  as::conv3x3_f32_psb(x.data_ptr<float>(), wsplit.data_ptr(), bp, rp, r2, r2 ? res2->numel() / Cout : 0, mk,
-                      out.data_ptr<float>(), static_cast<int>(B), static_cast<int>(H), static_cast<int>(W),
-                      static_cast<int>(Cin), static_cast<int>(Cout), static_cast<int>(act), stream());
-  return out;
+  as::conv3x3_f32_psb(a.x, a.wsplit, a.bias, a.res, a.res2, a.res2_rows, a.mask, a.out.data_ptr<float>(), a.B, a.H, a.W,
+                      a.Cin, a.Cout, static_cast<int>(act), stream());
+  return a.out;
 }
 
 at::Tensor conv3x3_f32_v2(const at::Tensor& x, const at::Tensor& wsplit, int64_t Cout,
-                           const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res,
-                           const c10::optional<at::Tensor>& res2, const c10::optional<at::Tensor>& mask, int64_t act,
+                          const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res,
+                          const c10::optional<at::Tensor>& res2, const c10::optional<at::Tensor>& mask, int64_t act,
                           int64_t variant) {
-  check_cuda(x, "x");
-  check_cuda(wsplit, "wsplit");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.dim() == 4 && x.is_contiguous(), "conv3x3_f32_psb: NHWC fp32 x");
-  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), M = B * H * W;
-  TORCH_CHECK(as::conv3x3_f32_psb_supported(M, static_cast<int>(Cin), static_cast<int>(Cout)),
-              "conv3x3_f32_psb: Cout % 128, Cin % 16");
-  TORCH_CHECK(wsplit.scalar_type() == at::kByte && wsplit.is_contiguous() &&
-                  wsplit.numel() == as::presplit_b_bytes(static_cast<int>(Cout), static_cast<int>(9 * Cin)),
-              "conv3x3_f32_psb: wsplit must be presplit_b of the [Cout, 9 Cin] weight");
-  auto fp = [&](const c10::optional<at::Tensor>& t, int64_t rows, const char* what) -> const float* {
-    if (!t || !t->defined()) return nullptr;
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->device() == x.device() &&
-                    (rows < 0 ? t->numel() == Cout : (t->numel() % Cout == 0 && t->numel() / Cout <= rows)), what);
-    return t->data_ptr<float>();
-  };
-  const float* bp = fp(bias, -1, "conv3x3_f32_psb: bias [Cout]");
-  const float* rp = fp(res, M, "conv3x3_f32_psb: res [B, H, W, Cout]");
-  if (rp) TORCH_CHECK(res->numel() == M * Cout, "conv3x3_f32_psb: res [B, H, W, Cout]");
-  const float* r2 = fp(res2, M, "conv3x3_f32_psb: res2 [b <= B, H, W, Cout]");
-  const float* mk = fp(mask, M, "conv3x3_f32_psb: mask [B, H, W, Cout]");
-  if (mk) TORCH_CHECK(mask->numel() == M * Cout, "conv3x3_f32_psb: mask [B, H, W, Cout]");
+  const ConvPsbArgs a = conv_psb_args("conv3x3_f32_v2", conv_psb_ok, "Cout % 128 (64 / 32 on the ring), Cin % 16", x,
+                                      wsplit, Cout, bias, res, res2, mask);
   c10::hip::HIPGuard g(x.device().index());
-  auto out = at::empty({B, H, W, Cout}, x.options());
-  as::conv3x3_f32_v2(x.data_ptr<float>(), wsplit.data_ptr(), bp, rp, r2, r2 ? res2->numel() / Cout : 0, mk,
-                      out.data_ptr<float>(), static_cast<int>(B), static_cast<int>(H), static_cast<int>(W),
-                      static_cast<int>(Cin), static_cast<int>(Cout), static_cast<int>(act),
-                     static_cast<int>(variant), stream());
-  return out;
+  as::conv3x3_f32_v2(a.x, a.wsplit, a.bias, a.res, a.res2, a.res2_rows, a.mask, a.out.data_ptr<float>(), a.B, a.H, a.W,
+                     a.Cin, a.Cout, static_cast<int>(act), static_cast<int>(variant), stream());
+  return a.out;
 }
 
-// the halo-window kernel (conv3x3_f32_halo.hip) directly, whatever conv_halo_f32_mode selects
 at::Tensor conv3x3_f32_halo(const at::Tensor& x, const at::Tensor& wsplit, int64_t Cout,
                             const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res,
                             const c10::optional<at::Tensor>& res2, const c10::optional<at::Tensor>& mask, int64_t act) {
-  check_cuda(x, "x");
-  check_cuda(wsplit, "wsplit");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && x.dim() == 4 && x.is_contiguous(), "conv3x3_f32_halo: NHWC fp32 x");
-  const int64_t B = x.size(0), H = x.size(1), W = x.size(2), Cin = x.size(3), M = B * H * W;
-  TORCH_CHECK(as::conv3x3_f32_psb_supported(M, static_cast<int>(Cin), static_cast<int>(Cout)) &&
-                  as::conv3x3_f32_halo_supported(static_cast<int>(H), static_cast<int>(W), static_cast<int>(Cin),
-                                                 static_cast<int>(Cout)),
-              "conv3x3_f32_halo: split mode, Cout 32 / 64 / % 128, Cin % 16, W <= 80");
-  TORCH_CHECK(wsplit.scalar_type() == at::kByte && wsplit.is_contiguous() &&
-                  wsplit.numel() == as::presplit_b_bytes(static_cast<int>(Cout), static_cast<int>(9 * Cin)),
-              "conv3x3_f32_halo: wsplit must be presplit_b of the [Cout, 9 Cin] weight");
-  auto fp = [&](const c10::optional<at::Tensor>& t, int64_t rows, const char* what) -> const float* {
-    if (!t || !t->defined()) return nullptr;
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->device() == x.device() &&
-                    (rows < 0 ? t->numel() == Cout : (t->numel() % Cout == 0 && t->numel() / Cout <= rows)), what);
-    return t->data_ptr<float>();
-  };
-  const float* bp = fp(bias, -1, "conv3x3_f32_halo: bias [Cout]");
-  const float* rp = fp(res, M, "conv3x3_f32_halo: res [B, H, W, Cout]");
-  if (rp) TORCH_CHECK(res->numel() == M * Cout, "conv3x3_f32_halo: res [B, H, W, Cout]");
-  const float* r2 = fp(res2, M, "conv3x3_f32_halo: res2 [b <= B, H, W, Cout]");
-  const float* mk = fp(mask, M, "conv3x3_f32_halo: mask [B, H, W, Cout]");
-  if (mk) TORCH_CHECK(mask->numel() == M * Cout, "conv3x3_f32_halo: mask [B, H, W, Cout]");
+  const ConvPsbArgs a = conv_psb_args("conv3x3_f32_halo", conv_halo_ok,
+                                      "split mode, Cout 32 / 64 / % 128, Cin % 16, W <= 80", x, wsplit, Cout, bias, res,
+                                      res2, mask);
   c10::hip::HIPGuard g(x.device().index());
-  auto out = at::empty({B, H, W, Cout}, x.options());
-  as::conv3x3_f32_halo(x.data_ptr<float>(), wsplit.data_ptr(), bp, rp, r2, r2 ? res2->numel() / Cout : 0, mk,
-                       out.data_ptr<float>(), static_cast<int>(B), static_cast<int>(H), static_cast<int>(W),
-                       static_cast<int>(Cin), static_cast<int>(Cout), static_cast<int>(act), stream());
-  return out;
+  as::conv3x3_f32_halo(a.x, a.wsplit, a.bias, a.res, a.res2, a.res2_rows, a.mask, a.out.data_ptr<float>(), a.B, a.H,
+                       a.W, a.Cin, a.Cout, static_cast<int>(act), stream());
+  return a.out;
 }
 
 bool conv3x3_f32_halo_supported(int64_t H, int64_t W, int64_t Cin, int64_t Cout) {

@@ -14,6 +14,18 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(8))) short bf16x8;  // MFMA A/B fragment (8 bf16)
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
 
+// byte offset past every buffer resource's range (num_records < 2^31 - 16): a buffer load / LDS-DMA from it
+// returns zeros
+constexpr int kOOB = 0x7ffffff0;
+
+// XCD-aware bijective remap of the flat workgroup id (8 XCDs, round-robin dispatch): consecutive logical ids share
+// an XCD's L2 (consecutive M-tiles of a conv share input halo rows)
+__device__ __forceinline__ int xcd_remap() {
+  const int nwg = gridDim.x, orig = blockIdx.x;
+  const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
+}
+
 __device__ __forceinline__ float bf2f(bf16_t v) {
   return __uint_as_float(static_cast<uint32_t>(v) << 16);
 }

@@ -28,7 +28,8 @@ typedef __attribute__((ext_vector_type(16))) float f16v;
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
-constexpr int kOOB = 0x7ffffff0;
+using as::kOOB;           // common.h
+using as::xcd_remap;
 
 // PIPE_ABL: timing-ablation bits for tools/native/gemm_f32_ablation.cpp only (1: fragments bit-cast instead of
 // split (wrong values, no split VALU), 2: no MFMAs); 0 in every library build
@@ -224,7 +225,7 @@ __device__ __forceinline__ void mainloop(char* const (&smem)[C::NS], i32x4 ar, i
 //   v = acc + bias[n] (+ res[m, n] | masked by res[m, n] > 0 for ACT_DRELU), then ReLU for ACT_RELU
 // Extra (input-gradient) terms: + res2[m, n] for rows m < res2_rows (a gradient handed over for the first rows
 // only, e.g. the location head's use of an encoder skip map), then the ReLU mask of the layer input:
-// v = mask[m, n] > 0 ? v : 0.
+// v = mask[m, n] > 0 ? v : 0.  An aggregate: pipe::Epi2{res2, res2_rows, mask}; Epi2() switches the extras off.
 struct Epi2 {
   const float* res2 = nullptr;
   long res2_rows = 0;
@@ -382,14 +383,6 @@ __device__ __forceinline__ void store_tile_staged(const f16v (&acc)[C::FM][C::FN
       }
     }
   }
-}
-
-// XCD-aware bijective remap of the workgroup id (8 XCDs, round-robin dispatch): consecutive logical ids share an
-// XCD's L2
-__device__ __forceinline__ int xcd_remap() {
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-  return (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
 }
 
 }  // namespace pipe

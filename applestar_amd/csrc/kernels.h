@@ -376,12 +376,19 @@ void multi_presplit(const PresplitArgs& a, hipStream_t s);
 void gemm_f32_psb(const float* a, const void* bsplit, const float* bias, const float* res, float* out, long M, int N,
                   int K, int act, int variant, hipStream_t s);
 // 3 x 3 conv on the pre-split planes of w [Cout, 3, 3, Cin] (presplit_b of its [Cout, 9 Cin] view); res2 / mask:
-// the input-gradient epilogue extras of conv3x3_f32_fwd_epi2 (nullptr: off)
+// the input-gradient epilogue extras of conv3x3_f32_fwd_epi2 (nullptr: off).  conv3x3_f32_psb picks the kernel -
+// halo window, LDS ring or register-streamed planes: the predicate, the switches (conv_halo_f32_mode,
+// APPLESTAR_CONV_V2) and the whole decision are in conv3x3_f32_dispatch.hip; the three launchers declared after it
+// run one kernel design each
 bool conv3x3_f32_psb_supported(long M, int Cin, int Cout);
 void conv3x3_f32_psb(const float* x, const void* wsplit, const float* bias, const float* res, const float* res2,
                      long res2_rows, const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int act,
                      hipStream_t s);
-// the same product with both operands staged through the LDS ring (conv3x3_f32_v2.hip; same support predicate)
+// the register-streamed weight planes (gemm_f32_psb.hip conv3x3_f32_psb_kernel): Cout % 128 == 0
+void conv3x3_f32_psb_stream(const float* x, const void* wsplit, const float* bias, const float* res,
+                            const float* res2, long res2_rows, const float* mask, float* out, int B, int H, int W,
+                            int Cin, int Cout, int act, hipStream_t s);
+// the same product with both operands staged through the LDS ring (conv3x3_f32_v2.hip; Cout % 128 == 0, 64 or 32)
 void conv3x3_f32_v2(const float* x, const void* wsplit, const float* bias, const float* res, const float* res2,
                     long res2_rows, const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int act,
                     int variant, hipStream_t s);
@@ -391,6 +398,7 @@ void gemm_f32_v2(const float* a, const void* bsplit, const float* bias, const fl
 // split mode, Cin % 16, Cout 32 / 64 / 128-multiples, W <= 80 (and the 32-bit bounds of conv3x3_f32_psb_supported).
 // conv_halo_f32_mode (APPLESTAR_CONV_HALO_F32): the output widths conv3x3_f32_psb sends there (bits: 1 = 32,
 // 2 = 64, 4 = 128-multiples; 0 = the ring kernel everywhere); _selected: supported and switched on for this width
+// (the mode and _selected: conv3x3_f32_dispatch.hip)
 bool conv3x3_f32_halo_supported(int H, int W, int Cin, int Cout);
 bool conv3x3_f32_halo_selected(int H, int W, int Cin, int Cout);
 int conv_halo_f32_mode();

@@ -23,6 +23,7 @@
 
 #include "../common.h"
 #include "../kernels.h"
+#include "../conv_tap.h"
 
 namespace as {
 namespace {
@@ -136,10 +137,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__
   const long M = static_cast<long>(B) * HW;
   const int K = 9 * Cin;
   const int ntn = (Cout + BN - 1) / BN;
-  // XCD-aware bijective remap of the flat workgroup id (8 XCDs, round-robin dispatch)
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
+  const int wg = xcd_remap();
   const int tn = wg % ntn;
   const long m0 = static_cast<long>(wg / ntn) * C::BM;
   const int n0 = tn * BN;
@@ -155,7 +153,6 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__
       const_cast<bf16_t*>(x), 0, static_cast<int>(M * Cin * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<bf16_t*>(w), 0, static_cast<int>(static_cast<long>(Cout) * K * 2), 0x00020000);
-  constexpr int kOOB = 0x7ffffff0;
 
   // per-thread A rows (fixed across K-steps): pixel index and a 9-bit in-image mask over the taps
   int a_pix[C::A_IT], a_row[C::A_IT], a_ch[C::A_IT], a_ok[C::A_IT];
@@ -166,16 +163,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__
     a_ch[i] = idx % C::CH;
     const long m = m0 + a_row[i];
     a_pix[i] = static_cast<int>(m);
-    a_ok[i] = 0;
-    if (m < M) {
-      const int rem = static_cast<int>(m % HW);
-      const int yy = rem / W, xx = rem - yy * W;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-        a_ok[i] |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
-      }
-    }
+    a_ok[i] = conv_tap_mask(m, M, HW, H, W);
   }
   int b_off[C::B_IT];
 #pragma unroll
@@ -192,18 +180,17 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__
 #pragma unroll
       for (int i = 0; i < C::A_IT; ++i) {
         const int k = k0 + 8 * a_ch[i];
-        const int tap = k / Cin, c = k - tap * Cin;
-        const int shift = (tap / 3 - 1) * W + (tap % 3 - 1);
-        const int off = (k < K && ((a_ok[i] >> tap) & 1)) ? ((a_pix[i] + shift) * Cin + c) * 2 : kOOB;
+        const ConvTap t = conv_tap(k, Cin, W);          // this piece's own tap
+        // t.offset() spelled out: through the helper these three instantiations allocate other register counts
+        const int off = (k < K && t.in(a_ok[i])) ? ((a_pix[i] + t.shift) * Cin + t.c0) * 2 : kOOB;
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0);
         ra[i] = make_uint4(v[0], v[1], v[2], v[3]);
       }
     } else {
-      const int tap = k0 / Cin, c0 = k0 - tap * Cin;
-      const int shift = (tap / 3 - 1) * W + (tap % 3 - 1);
+      const ConvTap t = conv_tap(k0, Cin, W);
 #pragma unroll
       for (int i = 0; i < C::A_IT; ++i) {
-        const int off = ((a_ok[i] >> tap) & 1) ? ((a_pix[i] + shift) * Cin + c0 + 8 * a_ch[i]) * 2 : kOOB;
+        const int off = t.offset(t.in(a_ok[i]), a_pix[i], Cin, 8 * a_ch[i], 2);
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0);
         ra[i] = make_uint4(v[0], v[1], v[2], v[3]);
       }
@@ -324,9 +311,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const bf16_t* __restr
   const long M = static_cast<long>(B) * HW;
   const int K = 9 * Cin;
   const int ntn = (Cout + BN - 1) / BN;
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
+  const int wg = xcd_remap();
   const int tn = wg % ntn;
   const long m0 = static_cast<long>(wg / ntn) * C::BM;
   const int n0 = tn * BN;
@@ -341,24 +326,11 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const bf16_t* __restr
       const_cast<bf16_t*>(x), 0, static_cast<int>(M * Cin * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<bf16_t*>(w), 0, static_cast<int>(static_cast<long>(Cout) * K * 2), 0x00020000);
-  constexpr int kOOB = 0x7ffffff0;
 
   // 9-bit in-image masks of this lane's A-fragment rows (pixel wm*TM + 16 i + lr of the tile)
   int ok9[C::FM];
 #pragma unroll
-  for (int i = 0; i < C::FM; ++i) {
-    const long m = m0 + wm * C::TM + 16 * i + lr;
-    ok9[i] = 0;
-    if (m < M) {
-      const int rem = static_cast<int>(m % HW);
-      const int yy = rem / W, xx = rem - yy * W;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-        ok9[i] |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
-      }
-    }
-  }
+  for (int i = 0; i < C::FM; ++i) ok9[i] = conv_tap_mask(m0 + wm * C::TM + 16 * i + lr, M, HW, H, W);
 
   uint4 rw[WP], rb[C::B_IT];
   auto load_win = [&](int c0) {

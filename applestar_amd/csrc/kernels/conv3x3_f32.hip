@@ -27,13 +27,12 @@
 #include "../kernels.h"
 #include "../split_mfma.h"
 #include "../f32_pipe.h"
+#include "../conv_tap.h"
 
 namespace as {
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f16v;
-
-constexpr int kOOB = 0x7ffffff0;
+using pipe::f16v;
 
 template <int BN_>
 struct ConvF32Cfg {
@@ -71,10 +70,7 @@ __global__ __launch_bounds__(256) void conv3x3_f32_kernel(const float* __restric
   const long M = static_cast<long>(B) * HW;
   const int K = 9 * Cin;
   const int ntn = (Cout + BN - 1) / BN;
-  // XCD-aware bijective remap (8 XCDs, round-robin dispatch): consecutive M-tiles share input halo rows
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
+  const int wg = xcd_remap();
   const int tn = wg % ntn;
   const long m0 = static_cast<long>(wg / ntn) * C::BM;
   const int n0 = tn * BN;
@@ -97,16 +93,7 @@ __global__ __launch_bounds__(256) void conv3x3_f32_kernel(const float* __restric
     a_c4[i] = C::pcol(idx);
     const long m = m0 + a_row[i];
     a_pix[i] = static_cast<int>(m);
-    a_ok[i] = 0;
-    if (m < M) {
-      const int rem = static_cast<int>(m % HW);
-      const int yy = rem / W, xx = rem - yy * W;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-        a_ok[i] |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
-      }
-    }
+    a_ok[i] = conv_tap_mask(m, M, HW, H, W);
   }
   int b_off[C::B_IT];
 #pragma unroll
@@ -119,11 +106,10 @@ __global__ __launch_bounds__(256) void conv3x3_f32_kernel(const float* __restric
   uint4 ra[C::A_IT], rb[C::B_IT];
   auto load_regs = [&](int kt) {
     const int k0 = kt * C::BK;
-    const int tap = k0 / Cin, c0 = k0 - tap * Cin;
-    const int shift = (tap / 3 - 1) * W + (tap % 3 - 1);
+    const ConvTap t = conv_tap(k0, Cin, W);
 #pragma unroll
     for (int i = 0; i < C::A_IT; ++i) {
-      const int off = ((a_ok[i] >> tap) & 1) ? ((a_pix[i] + shift) * Cin + c0 + 4 * a_c4[i]) * 4 : kOOB;
+      const int off = t.offset(t.in(a_ok[i]), a_pix[i], Cin, 4 * a_c4[i], 4);
       const auto v = __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0);
       ra[i] = make_uint4(v[0], v[1], v[2], v[3]);
     }
@@ -325,16 +311,7 @@ void conv3x3_f32_pipe_kernel(const float* __restrict__ x, const float* __restric
     const long m = m0 + row;
     a_c[c] = 4 * C::dma_piece(row, lane);
     a_pix[c] = static_cast<int>(m);
-    a_ok[c] = 0;
-    if (m < M) {
-      const int rem = static_cast<int>(m % HW);
-      const int yy = rem / W, xx = rem - yy * W;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-        a_ok[c] |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
-      }
-    }
+    a_ok[c] = conv_tap_mask(m, M, HW, H, W);
   }
 #pragma unroll
   for (int c = 0; c < C::B_PW; ++c) {
@@ -343,9 +320,8 @@ void conv3x3_f32_pipe_kernel(const float* __restrict__ x, const float* __restric
   }
   const int KT = K / 16;      // Cin % 16 == 0 (host check): every K-step lies inside one tap
   auto asrc = [&](int c, int kt) {
-    const int k0 = kt * 16, tap = k0 / Cin, c0 = k0 - tap * Cin;
-    const int shift = (tap / 3 - 1) * W + (tap % 3 - 1);
-    return kt < KT && ((a_ok[c] >> tap) & 1) ? ((a_pix[c] + shift) * Cin + c0 + a_c[c]) * 4 : pipe::kOOB;
+    const ConvTap t = conv_tap(kt * 16, Cin, W);
+    return t.offset(kt < KT && t.in(a_ok[c]), a_pix[c], Cin, a_c[c], 4);
   };
   auto bsrc = [&](int c, int kt) { return b_off[c] >= 0 && kt < KT ? b_off[c] + kt * 64 : pipe::kOOB; };
   f16v acc[C::FM][C::FN];
@@ -578,10 +554,7 @@ void conv3x3_f32_fwd_epi2(const float* x, const float* w, const float* res, cons
   const long M = static_cast<long>(B) * H * W;
   const long nwg = (M + 127) / 128 * (Cout / 128);
   if (nwg == 0) return;
-  pipe::Epi2 e2;
-  e2.res2 = res2;
-  e2.res2_rows = res2_rows;
-  e2.mask = mask;
+  const pipe::Epi2 e2{res2, res2_rows, mask};
   if (f32_conv_variant() == 3)
     hipLaunchKernelGGL((conv3x3_f32_pipe_kernel<128, 3, 128, false, 4, true>), dim3(static_cast<unsigned>(nwg)),
                        dim3(256), 0, s, x, w, nullptr, res, out, B, H, W, Cin, Cout, 0, e2);

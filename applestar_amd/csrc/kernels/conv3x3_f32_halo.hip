@@ -24,10 +24,14 @@
 // accumulator (mfma_x6(weights, activations)): pipe::store_tile and every epilogue of the ring kernel unchanged.
 // The summation order per output is chunk-major (the ring's is tap-major): results differ from the ring kernel's
 // in the last bits and are identical from run to run.
+//
+// This file: the kernel, its launcher (conv3x3_f32_halo) and what it covers (conv3x3_f32_halo_supported).  Which
+// convs conv3x3_f32_psb sends here: conv3x3_f32_dispatch.hip.  The in-image tap mask: conv_tap.h.
 #include "../common.h"
 #include "../kernels.h"
 #include "../split_mfma.h"
 #include "../f32_pipe.h"
+#include "../conv_tap.h"
 
 namespace as {
 namespace {
@@ -36,7 +40,6 @@ using pipe::f16v;
 using pipe::i32x4;
 
 constexpr int kHaloBM = 128, kHaloCK = 16, kHaloMaxW = 80;
-constexpr int kConvHaloF32Default = 7;      // the measured choice: docs/PERF_LOG.md
 
 // TS: taps per weight stage (1 / 3 / 9); WMAX: the widest map the window holds
 template <int BN, int TS, int WMAX>
@@ -92,16 +95,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f32_halo_kernel(const float* _
   int a_off[9];
   {
     const long m = m0 + wid * 32 + l32;
-    int ok = 0;
-    if (m < M) {
-      const int rem = static_cast<int>(m % HW);
-      const int yy = rem / W, xx = rem - yy * W;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-        ok |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
-      }
-    }
+    const int ok = conv_tap_mask(m, M, HW, H, W);
     const int r0 = wid * 32 + l32 + W + 1;
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
@@ -227,39 +221,18 @@ void launch_halo_f32_w(const float* x, const void* ws, const float* bias, const 
   else launch_halo_f32<BN, TS, kHaloMaxW>(x, ws, bias, res, e2, out, B, H, W, Cin, Cout, act, s);
 }
 
-// APPLESTAR_CONV_HALO_F32: which output widths conv3x3_f32_psb sends here (bits: 1 = 32, 2 = 64, 4 = 128-multiples;
-// 0 = none: the ring kernel everywhere)
-int& halo_f32_ref() {
-  static int v = [] {
-    const char* e = std::getenv("APPLESTAR_CONV_HALO_F32");
-    return e ? std::atoi(e) & 7 : kConvHaloF32Default;
-  }();
-  return v;
-}
-
 }  // namespace
-
-int conv_halo_f32_mode() { return halo_f32_ref(); }
-void set_conv_halo_f32_mode(int mode) { halo_f32_ref() = mode & 7; }
 
 bool conv3x3_f32_halo_supported(int H, int W, int Cin, int Cout) {
   return f32_mfma_mode() == 1 && H > 0 && W > 0 && W <= kHaloMaxW && Cin > 0 && Cin % kHaloCK == 0 &&
          (Cout == 32 || Cout == 64 || (Cout > 0 && Cout % 128 == 0));
 }
 
-bool conv3x3_f32_halo_selected(int H, int W, int Cin, int Cout) {
-  const int bit = Cout == 32 ? 1 : (Cout == 64 ? 2 : 4);
-  return (conv_halo_f32_mode() & bit) != 0 && conv3x3_f32_halo_supported(H, W, Cin, Cout);
-}
-
 void conv3x3_f32_halo(const float* x, const void* wsplit, const float* bias, const float* res, const float* res2,
                       long res2_rows, const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int act,
                       hipStream_t s) {
   if (static_cast<long>(B) * H * W == 0) return;
-  pipe::Epi2 e2;
-  e2.res2 = res2;
-  e2.res2_rows = res2_rows;
-  e2.mask = mask;
+  const pipe::Epi2 e2{res2, res2_rows, mask};
   // taps per weight stage, measured (docs/PERF_LOG.md): 64 outputs with one tap per stage (40 KB of LDS at W = 80:
   // four workgroups per CU) 470-490 us against 515-540 us with three (65 KB, two per CU) on the 76 x 80 32 -> 64
   // conv; 32 outputs the same either way (three: a third of the barriers); 128 outputs fit one tap only

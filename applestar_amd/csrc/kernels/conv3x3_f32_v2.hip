@@ -1,5 +1,6 @@
-// 3 x 3 / pad 1 convolution, fp32 operands, fp32-accurate bf16x6 split MFMAs (split_mfma.h), second design
-// (experimental, selected by variant): BOTH operands staged through one LDS-DMA ring per workgroup.
+// 3 x 3 / pad 1 convolution, fp32 operands, fp32-accurate bf16x6 split MFMAs (split_mfma.h), second design:
+// BOTH operands staged through one LDS-DMA ring per workgroup.  conv3x3_f32_psb's fallback where the halo-window
+// kernel is not selected (conv3x3_f32_dispatch.hip: the choice and the variant switch).
 //
 // conv3x3_f32_psb_kernel (gemm_f32_psb.hip) streams the pre-split weight planes straight from L2 into each wave's
 // registers: the two waves that share a weight fragment both load it, so a 128 x 128 tile moves 8 KB of activation
@@ -15,6 +16,7 @@
 #include "../kernels.h"
 #include "../split_mfma.h"
 #include "../f32_pipe.h"
+#include "../conv_tap.h"
 
 namespace as {
 namespace {
@@ -68,18 +70,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f32_v2_kernel(const float* __r
     const long m = m0 + row;
     a_c[c] = 4 * CA::dma_piece(row, lane);
     a_pix[c] = static_cast<int>(m);
-    a_ok[c] = 0;
-    if (!CONV) {
-      a_ok[c] = m < M;
-    } else if (m < M) {
-      const int rem = static_cast<int>(m % HW);
-      const int yy = rem / W, xx = rem - yy * W;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-        a_ok[c] |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
-      }
-    }
+    a_ok[c] = CONV ? conv_tap_mask(m, M, HW, H, W) : m < M;
   }
   // weight pieces: stage chunk q = wid + 4 c = (16-deep sub-step q / QB1, column block q % QB1 / 3, plane q % 3)
   constexpr int QB1 = kV2B1 / 1024;
@@ -94,12 +85,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f32_v2_kernel(const float* __r
     char* st = stage(kt);
     const int k0 = kt * BK;
     if constexpr (CONV) {
-      const int tap = k0 / Cin, c0 = k0 - tap * Cin;
-      const int shift = (tap / 3 - 1) * W + (tap % 3 - 1);
+      const ConvTap t = conv_tap(k0, Cin, W);
 #pragma unroll
       for (int c = 0; c < A_PW; ++c)
-        pipe::dma16(xr, st + (wid + 4 * c) * 1024,
-                    kt < KT && ((a_ok[c] >> tap) & 1) ? ((a_pix[c] + shift) * Cin + c0 + a_c[c]) * 4 : pipe::kOOB);
+        pipe::dma16(xr, st + (wid + 4 * c) * 1024, t.offset(kt < KT && t.in(a_ok[c]), a_pix[c], Cin, a_c[c], 4));
     } else {
 #pragma unroll
       for (int c = 0; c < A_PW; ++c)
@@ -168,10 +157,7 @@ void conv3x3_f32_v2(const float* x, const void* wsplit, const float* bias, const
                     long res2_rows, const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int act,
                     int variant, hipStream_t s) {
   if (static_cast<long>(B) * H * W == 0) return;
-  pipe::Epi2 e2;
-  e2.res2 = res2;
-  e2.res2_rows = res2_rows;
-  e2.mask = mask;
+  const pipe::Epi2 e2{res2, res2_rows, mask};
   if (Cout % 128 != 0) {        // 64 / 32 output channels: 128 x 64 / 128 x 32 tiles (each wave 32 rows), 2 stages
     // 32-deep K-steps per stage (half the barriers / DMA bookkeeping): 32 outputs 858 -> 743 us on the location
     // head's 76 x 80 64 -> 32 conv, but 64 outputs slower (574 -> 607, 634 -> 729 us; profiles/r10r_conv_narrow_sub*.jsonl)

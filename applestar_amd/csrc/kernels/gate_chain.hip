@@ -39,9 +39,7 @@ __global__ __launch_bounds__(256) void gate_chain_kernel(GateChainArgs a, long P
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1, lr = lane & 15, lg = lane >> 4;
   // bijective XCD-grouped tile order, as in the other tiled kernels
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wg = xcd_remap();
   const long m0 = static_cast<long>(wg) * kGRows;
   constexpr int PIECES = kGRows * kGC / 8 / 256;   // 16-B pieces per thread for a 128 x 128 tile (= 8)
 

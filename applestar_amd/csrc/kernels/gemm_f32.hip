@@ -30,8 +30,6 @@ namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f16v;
 
-constexpr int kOOB = 0x7ffffff0;
-
 // GF_ABL: timing-ablation bits for tools/native/gemm_f32_ablation.cpp only (1: no K-step loads after the first,
 // 2: no MFMAs (fragments kept live), 4: no epilogue stores); 0 in every library build
 #ifndef GF_ABL
@@ -71,9 +69,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
   using C = GemmF32Cfg<BN, BK>;
   __shared__ __attribute__((aligned(16))) float smem[2 * (SPLIT == 2 ? C::STAGE_S : C::STAGE)];
   const int ntn = (N + BN - 1) / BN;
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (orig >> 3);
+  const int wg = xcd_remap();
   const int tn = wg % ntn;
   const long m0 = static_cast<long>(wg / ntn) * C::BM;
   const int n0 = tn * BN;

@@ -11,10 +11,14 @@
 // fragments bypass LDS: each wave streams its two fragments straight into registers one K-step ahead (inline-asm
 // buffer loads counted with the ring's own vmcnt waits), while the LDS-DMA ring (f32_pipe.h) carries only the A
 // rows (8 KB a stage).  Per K-step a wave splits 2 fragments instead of 4; the LDS traffic per step halves.
+//
+// Also here: presplit_b / multi_presplit (the planes) and the 3 x 3 conv on the same loop (conv3x3_f32_psb_kernel,
+// launcher conv3x3_f32_psb_stream).  Which kernel a conv on pre-split planes runs: conv3x3_f32_dispatch.hip.
 #include "../common.h"
 #include "../kernels.h"
 #include "../split_mfma.h"
 #include "../f32_pipe.h"
+#include "../conv_tap.h"
 
 namespace as {
 namespace {
@@ -298,24 +302,13 @@ __global__ __launch_bounds__(256, 3) void conv3x3_f32_psb_kernel(const float* __
     const long m = m0 + row;
     a_c[c] = 4 * C::dma_piece(row, lane);
     a_pix[c] = static_cast<int>(m);
-    a_ok[c] = 0;
-    if (m < M) {
-      const int rem = static_cast<int>(m % HW);
-      const int yy = rem / W, xx = rem - yy * W;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-        a_ok[c] |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
-      }
-    }
+    a_ok[c] = conv_tap_mask(m, M, HW, H, W);
   }
   auto issue_a = [&](char* st, int kt) {
-    const int k0 = kt * 16, tap = k0 / Cin, c0 = k0 - tap * Cin;
-    const int shift = (tap / 3 - 1) * W + (tap % 3 - 1);
+    const ConvTap t = conv_tap(kt * 16, Cin, W);
 #pragma unroll
     for (int c = 0; c < A_PW; ++c)
-      pipe::dma16(xr, st + (wid + 4 * c) * 1024,
-                  kt < KT && ((a_ok[c] >> tap) & 1) ? ((a_pix[c] + shift) * Cin + c0 + a_c[c]) * 4 : pipe::kOOB);
+      pipe::dma16(xr, st + (wid + 4 * c) * 1024, t.offset(kt < KT && t.in(a_ok[c]), a_pix[c], Cin, a_c[c], 4));
   };
   const int nb0 = (n0 + wn * C::TN) / 32;
   int b_off[2];
@@ -365,45 +358,16 @@ void gemm_f32_psb(const float* a, const void* bsplit, const float* bias, const f
                        static_cast<const u32v4*>(bsplit), KT, bias, res, out, M, N, K, act);
 }
 
-int conv_v2_variant();
-// Cout % 128 (or 64 / 32 on the ring-staged kernel), Cin % 16 (every 16-deep K-step inside one tap), 32-bit offsets
-bool conv3x3_f32_psb_supported(long M, int Cin, int Cout) {
-  return (Cout % kPsbBN == 0 || ((Cout == 64 || Cout == 32) && conv_v2_variant() >= 0)) && Cin % 16 == 0 && Cin > 0 &&
-         M * Cin * 4 < 0x7ffffff0L &&
-         presplit_b_bytes(Cout, 9 * Cin) < 0x7ffffff0L && M * Cout < 0x7ffffff0L;
-}
-
-// APPLESTAR_CONV_V2: the design with both operands staged through the LDS ring (conv3x3_f32_v2.hip) and its
-// variant (default 2: 4 x 1 waves, 2 stages, 4 workgroups per CU: 218 vs 235 us on the ResBlock conv,
-// profiles/r8d_conv_v2.jsonl); -1 = the register-streamed weight planes below
-int conv_v2_variant() {
-  static const int v = [] {
-    const char* e = std::getenv("APPLESTAR_CONV_V2");
-    return e ? std::atoi(e) : 2;
-  }();
-  return v;
-}
-
-void conv3x3_f32_psb(const float* x, const void* wsplit, const float* bias, const float* res, const float* res2,
-                     long res2_rows, const float* mask, float* out, int B, int H, int W, int Cin, int Cout, int act,
-                     hipStream_t s) {
-  if (conv3x3_f32_halo_selected(H, W, Cin, Cout)) {       // the halo-window kernel where it is switched on
-    conv3x3_f32_halo(x, wsplit, bias, res, res2, res2_rows, mask, out, B, H, W, Cin, Cout, act, s);
-    return;
-  }
-  if (conv_v2_variant() >= 0) {
-    conv3x3_f32_v2(x, wsplit, bias, res, res2, res2_rows, mask, out, B, H, W, Cin, Cout, act, conv_v2_variant(), s);
-    return;
-  }
+// conv3x3_f32_psb_kernel: Cout % 128 == 0 (which conv takes it: conv3x3_f32_dispatch.hip)
+void conv3x3_f32_psb_stream(const float* x, const void* wsplit, const float* bias, const float* res, const float* res2,
+                            long res2_rows, const float* mask, float* out, int B, int H, int W, int Cin, int Cout,
+                            int act, hipStream_t s) {
   const long M = static_cast<long>(B) * H * W;
   const long nwg = (M + kPsbBM - 1) / kPsbBM * (Cout / kPsbBN);
   if (nwg == 0) return;
-  pipe::Epi2 e2;
-  e2.res2 = res2;
-  e2.res2_rows = res2_rows;
-  e2.mask = mask;
   hipLaunchKernelGGL(conv3x3_f32_psb_kernel, dim3(static_cast<unsigned>(nwg)), dim3(256), 0, s, x,
-                     static_cast<const u32v4*>(wsplit), bias, res, out, B, H, W, Cin, Cout, act, e2);
+                     static_cast<const u32v4*>(wsplit), bias, res, out, B, H, W, Cin, Cout, act,
+                     pipe::Epi2{res2, res2_rows, mask});
 }
 
 void multi_presplit(const PresplitArgs& a, hipStream_t s) {

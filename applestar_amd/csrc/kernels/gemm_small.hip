@@ -42,17 +42,16 @@ __device__ __forceinline__ void step_mfma(const float (&va)[8], const float (&vb
 // K % 4 fp32 / K % 8 bf16); a piece at or past K, or of a missing row, reads zeros (out-of-range offset)
 template <typename T>
 __device__ __forceinline__ void load8_vec(__amdgpu_buffer_rsrc_t r, long row, int k0, int K, float (&v)[8]) {
-  constexpr int kOOBv = 0x7ffffff0;
   if constexpr (sizeof(T) == 4) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const int off = row >= 0 && k0 + 4 * q < K ? static_cast<int>((row + k0 + 4 * q) * 4) : kOOBv;
+      const int off = row >= 0 && k0 + 4 * q < K ? static_cast<int>((row + k0 + 4 * q) * 4) : kOOB;
       const auto x = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[4 * q + j] = __uint_as_float(x[j]);
     }
   } else {
-    const int off = row >= 0 && k0 < K ? static_cast<int>((row + k0) * 2) : kOOBv;
+    const int off = row >= 0 && k0 < K ? static_cast<int>((row + k0) * 2) : kOOB;
     const auto x = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {

@@ -38,8 +38,6 @@ typedef __attribute__((ext_vector_type(4))) float f4;
 typedef __attribute__((ext_vector_type(4))) short s4;
 typedef __attribute__((address_space(3))) s4 lds_s4;
 
-constexpr int kOOB = 0x7ffffff0;
-
 template <int BN_, int BK_>
 struct WgCfg {
   static constexpr int BN = BN_, BK = BK_, BR = 64, NT = 256;
@@ -88,9 +86,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgBatch P, long part_s
 
   // XCD-aware remap: consecutive logical ids (the N x K tiles of one row slice, which read the same dY / X
   // rows) land on one XCD's L2
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wg = xcd_remap();
   const int tk = wg % tiles_k;
   const int tn = (wg / tiles_k) % tiles_n;
   const int s = wg / (tiles_k * tiles_n);

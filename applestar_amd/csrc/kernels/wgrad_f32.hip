@@ -22,8 +22,6 @@ namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f16v;
 
-constexpr int kOOB = 0x7ffffff0;
-
 template <int BN_, int BK_>
 struct WgF32Cfg {
   static constexpr int BN = BN_, BK = BK_, BR = 32, NT = 256;
@@ -45,9 +43,7 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const float* __restrict_
   using C = WgF32Cfg<BN, BK>;
   __shared__ __attribute__((aligned(16))) float smem[2 * C::STAGE];
 
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wg = xcd_remap();
   const int tk = wg % tiles_k;
   const int tn = (wg / tiles_k) % tiles_n;
   const int s = wg / (tiles_k * tiles_n);

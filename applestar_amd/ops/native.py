@@ -873,8 +873,8 @@ def embed_relu(table, idx):
 # rounded to bf16.
 def _conv3(x, wk, bias, res, act_code, w=None, dx=False, res2=None, mask=None):
     """3x3 / pad 1 conv on NHWC x with a [Cout, 3, 3, Cin] weight wk, epilogue act code (_ACT / 4 = ReLU mask).
-    ``w``: the conv parameter wk derives from (wk = _conv_w(w), or _conv_wt(w) for ``dx``): fp32 convs with 128-multiple
-    outputs then run on its pre-split planes (gemm_f32_psb.hip conv3x3_f32_psb_kernel).  res2 / mask: the extended
+    ``w``: the conv parameter wk derives from (wk = _conv_w(w), or _conv_wt(w) for ``dx``): the fp32 convs that
+    conv3x3_f32_psb covers then run on its pre-split planes (kernel choice: conv3x3_f32_dispatch.hip).  res2 / mask: the extended
     input-gradient epilogue (conv3x3_f32_epi2)."""
     if x.dtype == torch.float32:
         B, H, W, Cin = x.shape

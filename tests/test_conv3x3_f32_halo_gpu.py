@@ -150,6 +150,39 @@ def test_two_launches_bit_identical(shape):
     assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize('entry', ['conv3x3_f32_psb', 'conv3x3_f32_v2', 'conv3x3_f32_halo'])
+def test_presplit_entries_validate_operands(entry):
+    """The three pre-split entry points share one operand check: each refuses short planes, a strided x, a bias or
+    residual of the wrong size and Cin = 8 with a message that starts with its own name, and still runs the valid
+    call."""
+    C = _C()
+    shape = (1, 2, 20, 16, 32)
+    B, H, W, Ci, Co = shape
+    t = _case(shape)
+    d = {k: v.to(DEV) for k, v in t.items() if k != 'conv'}
+    ws = C.presplit_b(d['w'].reshape(Co, -1).contiguous())
+    fn = getattr(C, entry)
+    extra = (2,) if entry == 'conv3x3_f32_v2' else ()       # the ring entry's variant
+
+    def call(x=d['x'], ws=ws, co=Co, bias=d['bias'], res=d['res']):
+        return fn(x, ws, co, bias, res, None, None, 0, *extra)
+
+    x8 = torch.zeros(B, H, W, 8, device=DEV)
+    w8 = torch.zeros(Co, 3, 3, 8, device=DEV)
+    bad = {
+        'short wsplit': dict(ws=ws[:-1].contiguous()),
+        'strided x': dict(x=torch.zeros(B, H, W, 2 * Ci, device=DEV)[..., ::2]),
+        'bias Cout + 1': dict(bias=torch.zeros(Co + 1, device=DEV)),
+        'res of another size': dict(res=torch.zeros(B, H, W - 1, Co, device=DEV)),
+        'Cin = 8': dict(x=x8, ws=C.presplit_b(w8.reshape(Co, -1).contiguous())),
+    }
+    for what, kw in bad.items():
+        with pytest.raises(RuntimeError) as e:
+            call(**kw)
+        assert str(e.value).startswith(entry + ':'), (what, str(e.value))
+    _check(call(), _reference(t, 'res'))
+
+
 @pytest.mark.parametrize('shape', SHAPES)
 def test_psb_switch_on_and_off_agree(shape):
     """conv3x3_f32_psb with the halo kernel switched off (the ring kernel) and on: same split products, another
