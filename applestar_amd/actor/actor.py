@@ -16,6 +16,9 @@ MI355X structure:
   worker's policy and teacher requests (dynamic batching, no polling); workers hold no model;
 * trajectories go worker -> learner directly through each worker's own :class:`Adapter`
   (producer-side payload server), never through the parent;
+* DAPO (``learner.use_dapo``): a training job's ``successive_ids`` / ``successive_checkpoint_paths`` name the lagged
+  copy of a main player's checkpoint; it is loaded like a teacher (policy weights, eval mode) and its logits for
+  the sampled action go into the trajectory as ``successive_logit``;
 * model refresh: the parent pulls ``<player>model`` broadcasts every ``actor_model_update_interval``
   seconds and hot-loads them into the server's resident models.
 """
@@ -45,6 +48,7 @@ DEFAULT_ACTOR_CONFIG = {
               'env_num': 1, 'episode_num': 1, 'print_freq': 100, 'traj_len': 64, 'use_cuda': False,
               'fake_model': True, 'player_ids': ['model1'], 'agents': {}, 'model_paths': {},
               'teacher_player_ids': ['none'], 'teacher_model_paths': {}, 'max_wait_ms': 2.0,
+              'successive_player_ids': ['none'], 'successive_model_paths': {},
               # env workers run at this nice level: on a box shared with a learner / inference server the host
               # threads that feed the GPU keep their CPU (0: unchanged)
               'env_nice': 5},
@@ -72,6 +76,18 @@ def load_policy_weights(model: torch.nn.Module, path: str, agent: Optional[Agent
     return int(sd.get('last_iter', 0))
 
 
+def successive_of(cfg, job: dict, idx: int):
+    """(successive id, checkpoint path) of seat ``idx`` of a training job under DAPO, else None."""
+    if not cfg.learner.get('use_dapo', False) or 'train' not in cfg.actor.job_type:
+        return None
+    ids, paths = job.get('successive_ids') or [], job.get('successive_checkpoint_paths') or []
+    sid = ids[idx] if idx < len(ids) else 'none'
+    path = paths[idx] if idx < len(paths) else 'none'
+    if sid in _NO_CKPT or path in _NO_CKPT:
+        return None
+    return sid, path
+
+
 def make_env(cfg):
     """Real SC2 when available and not forced fake, else :class:`FakeSC2Env`."""
     from ..envs import make_env as _make
@@ -85,6 +101,8 @@ def _job_from_config(cfg) -> dict:
     teacher_ids = list(a.get('teacher_player_ids', ['none'] * len(ids)))
     teacher_ids += ['none'] * (len(ids) - len(teacher_ids))
     model_ids = list(a.player_ids) + ['none'] * len(ids)
+    succ_ids = list(a.get('successive_player_ids', []))
+    succ_ids += ['none'] * (len(ids) - len(succ_ids))
     return {'player_ids': [model_ids[i] if 'bot' not in ids[i] else ids[i] for i in range(len(ids))],
             'side_ids': list(range(len(ids))),
             'pipelines': ['bot' if 'bot' in p else a.agents.get(model_ids[i], 'default') for i, p in enumerate(ids)],
@@ -93,13 +111,14 @@ def _job_from_config(cfg) -> dict:
             'teacher_checkpoint_paths': [a.teacher_model_paths.get(t, 'none') for t in teacher_ids],
             'z_path': [cfg.get('agent', {}).get('z_path', '7map_filter_spine.json')] * len(ids),
             'z_prob': [cfg.get('agent', {}).get('fake_reward_prob', 1.0)] * len(ids),
-            'send_data_players': [], 'update_players': [], 'successive_ids': ['none'] * len(ids),
+            'send_data_players': [], 'update_players': [], 'successive_ids': succ_ids,
+            'successive_checkpoint_paths': [a.get('successive_model_paths', {}).get(s, 'none') for s in succ_ids],
             'env_info': {'player_ids': ids}}
 
 
 def build_agents(cfg, job: dict, clients: Optional[Dict] = None) -> List[Agent]:
     """One Agent per non-bot seat; models shared per player id (or remote through ``clients``)."""
-    agents, models, teachers = [], {}, {}
+    agents, models, teachers, successives = [], {}, {}, {}
     for idx, pid in enumerate(job['player_ids']):
         if 'bot' in job['pipelines'][idx]:
             continue
@@ -132,8 +151,15 @@ def build_agents(cfg, job: dict, clients: Optional[Dict] = None) -> List[Agent]:
                     if not cfg.actor.fake_model:
                         load_policy_weights(teachers[tid], job['teacher_checkpoint_paths'][idx])
                 teacher = teachers[tid]
-            agent = Agent(acfg, model=models[pid], teacher_model=teacher or (models[pid]
-                                                                             if 'train' in cfg.actor.job_type else None))
+            succ = successive_of(cfg, job, idx)
+            if succ is not None and succ not in successives:
+                from ..models.model import Model
+                successives[succ] = Model(acfg).eval()
+                if not cfg.actor.fake_model:
+                    load_policy_weights(successives[succ], succ[1])
+            if teacher is None and 'train' in cfg.actor.job_type:
+                teacher = models[pid]
+            agent = Agent(acfg, model=models[pid], teacher_model=teacher, successive_model=successives.get(succ))
         agent.player_id = pid
         agent.side_id = job['side_ids'][idx]
         agent._fake_reward_prob = job['z_prob'][idx]
@@ -235,8 +261,9 @@ def _worker_main(cfg_dict, job, env_id, req_conns, ctrl, result_q, coord):
     clients = None
     if req_conns is not None:
         clients = {}
-        for (pid, key_kind), (conn, kind, tkey) in req_conns.items():
-            clients[(pid, key_kind)] = InferenceClient(conn, pid, kind, teacher_id=tkey)
+        for (pid, key_kind), (conn, kind, tkey, *sid) in req_conns.items():
+            clients[(pid, key_kind)] = InferenceClient(conn, pid, kind, teacher_id=tkey,
+                                                       successive_id=sid[0] if sid else None)
     adapter = None
     if coord is not None and cfg.actor.job_type == 'train':
         from ..comm.adapter import Adapter
@@ -307,6 +334,12 @@ class Actor:
                         if not self._cfg.fake_model:
                             load_policy_weights(t, job['teacher_checkpoint_paths'][idx])
                         self._server.set_model(tid, t, teacher=True)
+                succ = successive_of(self._whole_cfg, job, idx)
+                if succ is not None and succ[0] not in self._server.successive:
+                    u = Model(self._whole_cfg).eval()
+                    if not self._cfg.fake_model:
+                        load_policy_weights(u, succ[1])
+                    self._server.set_model(succ[0], u, successive=True)
         coord = None
         if self._comm is not None:
             coord = (self._whole_cfg.communication.coordinator_ip, self._whole_cfg.communication.coordinator_port)
@@ -325,8 +358,10 @@ class Actor:
                     if (pid, 'policy') in req:
                         continue
                     parent, child = ctx.Pipe()
-                    self._server.add_connection(parent, route=(pid, kind, tkey if kind != 'policy' else None))
-                    req[(pid, 'policy')] = (child, kind, tkey)
+                    succ = successive_of(self._whole_cfg, job, idx) if kind != 'policy' else None
+                    sid = (succ[0],) if succ is not None else ()
+                    self._server.add_connection(parent, route=(pid, kind, tkey if kind != 'policy' else None) + sid)
+                    req[(pid, 'policy')] = (child, kind, tkey) + sid
             p_ctrl, c_ctrl = ctx.Pipe()
             p = ctx.Process(target=_worker_main, daemon=True,
                             args=(dict(self._whole_cfg), job, env_id, req, c_ctrl, self._result_q, coord))

@@ -16,6 +16,9 @@ MI355X design:
   the teacher's teacher-forced logits for that very action are computed in the same HIP graph (the
   reference's two round trips per agent step become one; ``agent.py`` caches the teacher half for
   ``collect_data``);
+* DAPO: a 'policy+teacher' route may name a fourth element, the id of a successive model (a lagged copy of the
+  player's own checkpoint); its teacher-forced logits for the sampled action, with its own LSTM state, ride in
+  the same request and graph (reply key ``successive``);
 * every (route, batch bucket, entity bucket) is a captured HIP graph (``runtime.graphs.GraphedPolicy``);
 * two-stage pipeline: a batch is LAUNCHED (H2D, replay, async D2H into pinned memory, event) and FINISHED
   (event wait, per-row replies) on the next loop turn, after the next batch was collected and launched -
@@ -66,37 +69,46 @@ class InferenceClient:
     model input; routes registered without a key get the self-describing envelope."""
 
     def __init__(self, conn: Connection, player_id: str, kind: str = 'policy', teacher_id: Optional[str] = None,
-                 routed: bool = True):
+                 routed: bool = True, successive_id: Optional[str] = None):
         self._conn = conn
         self.player_id = player_id
         self.kind = kind
         self.teacher_id = teacher_id
+        self.successive_id = successive_id
         self.routed = routed
 
     def infer(self, model_input: Dict) -> Dict:
         if self.routed:
             self._conn.send_bytes(serialize.dumps(model_input))
         else:
-            self._conn.send_bytes(serialize.dumps({'player_id': self.player_id, 'kind': self.kind,
-                                                   'teacher_id': self.teacher_id, 'input': model_input}))
+            env = {'player_id': self.player_id, 'kind': self.kind, 'teacher_id': self.teacher_id, 'input': model_input}
+            if self.successive_id is not None:
+                env['successive_id'] = self.successive_id
+            self._conn.send_bytes(serialize.dumps(env))
         return serialize.loads(self._conn.recv_bytes())
 
 
 class _PolicyTeacher(torch.nn.Module):
     """One agent step of a training actor: policy sample + the teacher's logits for the sampled action
-    (``compute_logp_action`` then ``compute_teacher_logit`` with the teacher's own LSTM state)."""
+    (``compute_logp_action`` then ``compute_teacher_logit`` with the teacher's own LSTM state); with a successive
+    model (DAPO) also that model's logits for the same action, with its own LSTM state."""
 
-    def __init__(self, policy, teacher):
+    def __init__(self, policy, teacher, successive=None):
         super().__init__()
-        self.policy, self.teacher = policy, teacher
+        self.policy, self.teacher, self.successive = policy, teacher, successive
 
     def step(self, spatial_info, entity_info, scalar_info, entity_num, hidden_state, teacher_hidden_state,
-             noise=None, **kwargs):
+             noise=None, successive_hidden_state=None, **kwargs):
         out = self.policy.compute_logp_action(spatial_info, entity_info, scalar_info, entity_num, hidden_state,
                                               noise=noise)
         t = self.teacher.compute_teacher_logit(spatial_info, entity_info, scalar_info, entity_num,
                                                teacher_hidden_state, out['selected_units_num'], out['action_info'])
         out['teacher'] = {'logit': t['logit'], 'hidden_state': t['hidden_state']}
+        if self.successive is not None:
+            u = self.successive.compute_teacher_logit(spatial_info, entity_info, scalar_info, entity_num,
+                                                      successive_hidden_state, out['selected_units_num'],
+                                                      out['action_info'])
+            out['successive'] = {'logit': u['logit'], 'hidden_state': u['hidden_state']}
         return out
 
 
@@ -127,6 +139,7 @@ class InferenceServer:
             if self.device.type == 'cuda' and prio != 0 else None
         self.models: Dict[str, torch.nn.Module] = {}
         self.teachers: Dict[str, torch.nn.Module] = {}
+        self.successive: Dict[str, torch.nn.Module] = {}
         self.model_iter: Dict[str, int] = defaultdict(int)
         self._conns: List[Connection] = []
         self._routes: Dict[Connection, Optional[tuple]] = {}
@@ -136,7 +149,7 @@ class InferenceServer:
         self.stats = defaultdict(float)
 
     # ------------------------------------------------------------------ models
-    def set_model(self, player_id: str, model: torch.nn.Module, teacher: bool = False):
+    def set_model(self, player_id: str, model: torch.nn.Module, teacher: bool = False, successive: bool = False):
         model = model.to(self.device).eval()
         if self.device.type == 'cuda' and getattr(model, '_inference_forms', None) is None:
             # bf16 / transposed weight forms cast once per weight version, not inside every graph replay
@@ -144,9 +157,10 @@ class InferenceServer:
             if native.ensure_loaded() is not None:
                 model._inference_forms = native.attach_inference_forms(model)
         with self._lock:
-            (self.teachers if teacher else self.models)[player_id] = model
-            self._graphed = {k: v for k, v in self._graphed.items() if player_id not in k[0][::2]}
-            self._runners = {k: v for k, v in self._runners.items() if player_id not in k[::2]}
+            (self.successive if successive else self.teachers if teacher else self.models)[player_id] = model
+            # routes are (player, kind, teacher[, successive]): drop what was built on any of the ids
+            self._graphed = {k: v for k, v in self._graphed.items() if player_id not in k[0][:1] + k[0][2:]}
+            self._runners = {k: v for k, v in self._runners.items() if player_id not in k[:1] + k[2:]}
 
     def load_state_dict(self, player_id: str, state_dict: Dict, teacher: bool = False, last_iter: int = 0):
         """Hot model update (weights pulled from the learner) without rebuilding the module.  Captured graphs
@@ -246,15 +260,17 @@ class InferenceServer:
         return out
 
     def add_connection(self, conn: Connection, route: Optional[Tuple[str, str, Optional[str]]] = None):
-        """``route`` = (player_id, kind, teacher_id): requests on ``conn`` are bare model inputs for that route
-        (kind 'policy', 'teacher' or 'policy+teacher'); None: self-describing envelopes."""
+        """``route`` = (player_id, kind, teacher_id[, successive_id]): requests on ``conn`` are bare model inputs
+        for that route (kind 'policy', 'teacher' or 'policy+teacher'; the optional successive id only with
+        'policy+teacher'); None: self-describing envelopes."""
         with self._lock:
             self._conns.append(conn)
             self._routes[conn] = tuple(route) if route is not None else None
 
     # ------------------------------------------------------------------ execution
     def _runner(self, route) -> Tuple[torch.nn.Module, str]:
-        pid, kind, tid = route
+        pid, kind, tid = route[:3]
+        sid = route[3] if len(route) > 3 else None
         with self._lock:
             if kind == 'policy':
                 return self.models[pid], 'compute_logp_action'
@@ -262,7 +278,8 @@ class InferenceServer:
                 return self.teachers[pid], 'compute_teacher_logit'
             r = self._runners.get(route)
             if r is None:
-                r = self._runners[route] = _PolicyTeacher(self.models[pid], self.teachers[tid or pid])
+                r = self._runners[route] = _PolicyTeacher(self.models[pid], self.teachers[tid or pid],
+                                                          self.successive[sid] if sid is not None else None)
             return r, 'step'
 
     def _bucket(self, n: int) -> int:
@@ -343,8 +360,9 @@ class InferenceServer:
         trims = {'logit/selected_units': [(0, s), (1, e1)], 'logit/target_unit': [(0, e)],
                  'action_info/selected_units': [(0, s)], 'action_logp/selected_units': [(0, s)],
                  'extra_units': [(0, e)],
-                 'teacher/logit/selected_units': [(0, s), (1, e1)], 'teacher/logit/target_unit': [(0, e)]}
-        pid, kind, _ = L.route
+                 'teacher/logit/selected_units': [(0, s), (1, e1)], 'teacher/logit/target_unit': [(0, e)],
+                 'successive/logit/selected_units': [(0, s), (1, e1)], 'successive/logit/target_unit': [(0, e)]}
+        pid, kind = L.route[:2]
         if kind != 'teacher':
             out['model_last_iter'] = self.model_iter[pid]
         frames = nat.rows_dumps(out, n, trims)
@@ -354,14 +372,16 @@ class InferenceServer:
     def _results(self, L: _Launched) -> List[Dict]:
         t1 = self._wait(L)
         out = L.out
-        teacher = out.pop('teacher', None)
+        halves = {k: out.pop(k, None) for k in ('teacher', 'successive')}
         res = [decollate_output(out, i) for i in range(L.n)]
-        if teacher is not None:
-            t = dict(teacher, entity_num=out['entity_num'], selected_units_num=out['selected_units_num'])
+        for name, half in halves.items():
+            if half is None:
+                continue
+            t = dict(half, entity_num=out['entity_num'], selected_units_num=out['selected_units_num'])
             for i, r in enumerate(res):
                 td = decollate_output(t, i)
-                r['teacher'] = {'logit': td['logit'], 'hidden_state': td['hidden_state']}
-        pid, kind, _ = L.route
+                r[name] = {'logit': td['logit'], 'hidden_state': td['hidden_state']}
+        pid, kind = L.route[:2]
         if kind != 'teacher':
             for r in res:
                 r['model_last_iter'] = self.model_iter[pid]
@@ -381,10 +401,12 @@ class InferenceServer:
         if self._stream is not None:
             self._stream.wait_stream(torch.cuda.current_stream(self.device))
 
-    def _forward(self, player_id: str, kind: str, inputs: List[Dict], teacher_id: Optional[str] = None) -> List[Dict]:
+    def _forward(self, player_id: str, kind: str, inputs: List[Dict], teacher_id: Optional[str] = None,
+                 successive_id: Optional[str] = None) -> List[Dict]:
         """Synchronous batch of decoded inputs (tests / in-process callers); replies keep the policy logits."""
+        route = (player_id, kind, teacher_id) + ((successive_id,) if successive_id is not None else ())
         with self._on_stream():
-            return self._results(self._launch((player_id, kind, teacher_id), inputs=inputs, keep_logits=True))
+            return self._results(self._launch(route, inputs=inputs, keep_logits=True))
 
     # ------------------------------------------------------------------ serving
     def _finish(self, L: _Launched):
@@ -452,6 +474,8 @@ class InferenceServer:
             if route is None:                       # envelope: decode to find the route
                 req = serialize.loads(frame)
                 route = (req['player_id'], req['kind'], req.get('teacher_id'))
+                if req.get('successive_id') is not None:
+                    route += (req['successive_id'],)
                 frame = serialize.dumps(req['input'])
             groups[route].append((c, frame))
         return groups

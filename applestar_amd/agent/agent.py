@@ -58,7 +58,7 @@ class Agent:
     HAS_SUCCESSIVE_MODEL = False
 
     def __init__(self, cfg=None, env_id: int = 0, model=None, teacher_model=None, inference_client=None,
-                 teacher_client=None):
+                 teacher_client=None, successive_model=None):
         self._whole_cfg = deep_merge_dicts(DEFAULT_AGENT_CONFIG, cfg or {})
         c = self._whole_cfg
         self._job_type = c.actor.job_type
@@ -85,6 +85,9 @@ class Agent:
         # reply (one round trip per agent step); collect_data then uses the cached half
         self._merged = inference_client is not None and getattr(inference_client, 'kind', '') == 'policy+teacher'
         self._teacher_out = None
+        # DAPO: a merged client bound to a successive model also returns that model's logits for the sampled action
+        self._merged_successive = self._merged and getattr(inference_client, 'successive_id', None) is not None
+        self._successive_out = None
         self.z_idx = None
         if model is None and inference_client is None:
             from ..models.model import Model
@@ -98,7 +101,11 @@ class Agent:
         if 'train' in self._job_type and teacher_model is None and teacher_client is None and not self._merged:
             from ..models.model import Model
             self.teacher_model = Model(c).eval()
-        self.successive_model = None
+        self.successive_model = successive_model
+        if self.successive_model is not None:
+            self.successive_model.eval()
+            if self._use_cuda:
+                self.successive_model.cuda()
         self._num_layers = 3
         self._hidden_size = 384
         self._reset_z_defaults()
@@ -285,8 +292,11 @@ class Agent:
             req = self._model_input(agent_obs)
             if self._merged:
                 req['teacher_hidden_state'] = self._teacher_hidden_state
+            if self._merged_successive:
+                req['successive_hidden_state'] = self._successive_hidden_state
             out = self._client.infer(req)
             self._teacher_out = out.pop('teacher', None)
+            self._successive_out = out.pop('successive', None)
             self._model_last_iter = int(out.pop('model_last_iter', self._model_last_iter))
         else:
             batch = collate_obs([self._model_input(agent_obs)])
@@ -393,9 +403,15 @@ class Agent:
                 batch = _to(batch, 'cuda')
             t_out = decollate_output(self.teacher_model.compute_teacher_logit(**batch), 0)
         self._teacher_hidden_state = t_out['hidden_state']
-        if self._use_dapo and self.successive_model is not None:
-            s_in = dict(teacher_in, hidden_state=self._successive_hidden_state)
-            s_out = decollate_output(self.successive_model.compute_teacher_logit(**collate_obs([s_in])), 0)
+        s_out = None
+        if self._successive_out is not None:     # computed with the policy step (merged request)
+            s_out, self._successive_out = self._successive_out, None
+        elif self._use_dapo and self.successive_model is not None:
+            batch = collate_obs([dict(teacher_in, hidden_state=self._successive_hidden_state)])
+            if self._use_cuda:
+                batch = _to(batch, 'cuda')
+            s_out = decollate_output(self.successive_model.compute_teacher_logit(**batch), 0)
+        if s_out is not None:
             self._successive_hidden_state = s_out['hidden_state']
 
         ai = {k: v.clone() for k, v in self._output['action_info'].items()}
@@ -419,7 +435,7 @@ class Agent:
             'step': torch.tensor(float(self._game_step)), 'mask': mask}
         if self._use_value_feature:
             step_data['value_feature'] = dict(agent_obs['value_feature'], **behaviour_z)
-        if self._use_dapo and self.successive_model is not None:
+        if s_out is not None:
             step_data['successive_logit'] = s_out['logit']
         self._hidden_state_backup = self._hidden_state
         self._data_buffer.append(step_data)

@@ -109,13 +109,16 @@ def _pad_step(step: Dict, n: int) -> Dict:
         s['behaviour_logp'] = dict(step['behaviour_logp'])
         s['behaviour_logp']['selected_units'] = _pad_last(step['behaviour_logp']['selected_units'],
                                                           MAX_SELECTED_UNITS_NUM, NEG)
-        tl = dict(step['teacher_logit'])
-        su = tl['selected_units']
-        su = su.reshape(-1, su.shape[-1]) if su.numel() else su.new_zeros(0, en + 1)
-        tl['selected_units'] = F.pad(su, (0, n + 1 - su.shape[-1], 0, MAX_SELECTED_UNITS_NUM - su.shape[0]),
-                                     value=NEG)
-        tl['target_unit'] = _pad_last(tl['target_unit'], n, NEG)
-        s['teacher_logit'] = tl
+        for key in ('teacher_logit', 'successive_logit'):
+            if key not in step:           # successive_logit: only steps of a DAPO actor carry it
+                continue
+            tl = dict(step[key])
+            su = tl['selected_units']
+            su = su.reshape(-1, su.shape[-1]) if su.numel() else su.new_zeros(0, en + 1)
+            tl['selected_units'] = F.pad(su, (0, n + 1 - su.shape[-1], 0, MAX_SELECTED_UNITS_NUM - su.shape[0]),
+                                         value=NEG)
+            tl['target_unit'] = _pad_last(tl['target_unit'], n, NEG)
+            s[key] = tl
         m = dict(step['mask'])
         ar = torch.arange(MAX_SELECTED_UNITS_NUM)
         m['selected_units_mask'] = ar < int(su_num)

@@ -1893,8 +1893,10 @@ std::vector<at::Tensor> resmlp_bwd(const at::Tensor& dout, const std::vector<at:
 // ---------------------------------------------------------------- fused categorical head statistics
 // logits [R, C] fp32/bf16, teacher [R, C] fp32/bf16 (optional), action [R] int64
 // -> out [3, R] fp32 (logp_a, entropy, KL(teacher || logits)), stats [R, 6] fp32
+// with successive [R, C] (the teacher's dtype when both are given): out [4, R] (..., KL(successive || logits)),
+// stats [R, 8]
 std::vector<at::Tensor> head_stats_fwd(const at::Tensor& logits, const c10::optional<at::Tensor>& teacher,
-                                       const at::Tensor& action) {
+                                       const at::Tensor& action, const c10::optional<at::Tensor>& successive) {
   check_cuda(logits, "logits");
   check_cuda(action, "action");
   TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "head_stats: logits [R, C] contiguous");
@@ -1914,6 +1916,19 @@ std::vector<at::Tensor> head_stats_fwd(const at::Tensor& logits, const c10::opti
     tdt = dt(t);
   }
   c10::hip::HIPGuard g(logits.device().index());
+  if (successive.has_value()) {
+    const at::Tensor& u = *successive;
+    check_cuda(u, "successive");
+    TORCH_CHECK(u.sizes() == logits.sizes() && u.is_contiguous(), "head_stats: successive [R, C] contiguous");
+    TORCH_CHECK(u.scalar_type() == at::kFloat || u.scalar_type() == at::kBFloat16, "head_stats: successive dtype");
+    TORCH_CHECK(!teacher.has_value() || teacher->scalar_type() == u.scalar_type(),
+                "head_stats: teacher and successive share one dtype");
+    auto out = at::empty({4, R}, logits.options().dtype(at::kFloat));
+    auto stats = at::empty({R, 8}, logits.options().dtype(at::kFloat));
+    as::head_stats2_fwd(logits.data_ptr(), dt(logits), tp, u.data_ptr(), dt(u), action.data_ptr<int64_t>(),
+                        out.data_ptr<float>(), stats.data_ptr<float>(), R, static_cast<int>(C), stream());
+    return {out, stats};
+  }
   auto out = at::empty({3, R}, logits.options().dtype(at::kFloat));
   auto stats = at::empty({R, 6}, logits.options().dtype(at::kFloat));
   as::head_stats_fwd(logits.data_ptr(), dt(logits), tp, tdt, action.data_ptr<int64_t>(), out.data_ptr<float>(),
@@ -1922,17 +1937,28 @@ std::vector<at::Tensor> head_stats_fwd(const at::Tensor& logits, const c10::opti
 }
 
 at::Tensor head_stats_bwd(const at::Tensor& logits, const c10::optional<at::Tensor>& teacher, const at::Tensor& action,
-                          const at::Tensor& stats, const at::Tensor& grad) {
+                          const at::Tensor& stats, const at::Tensor& grad,
+                          const c10::optional<at::Tensor>& successive) {
   check_cuda(grad, "grad");
-  TORCH_CHECK(grad.scalar_type() == at::kFloat && grad.is_contiguous() && grad.numel() == 3 * logits.size(0),
-              "head_stats_bwd: grad fp32 [3, R]");
-  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.is_contiguous() && stats.numel() == 6 * logits.size(0),
+  const int64_t no = successive.has_value() ? 4 : 3, sw = successive.has_value() ? 8 : 6;
+  TORCH_CHECK(grad.scalar_type() == at::kFloat && grad.is_contiguous() && grad.numel() == no * logits.size(0),
+              "head_stats_bwd: grad fp32 [3, R] ([4, R] with successive)");
+  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.is_contiguous() && stats.numel() == sw * logits.size(0),
               "head_stats_bwd: stats");
   const int64_t R = logits.size(0), C = logits.size(1);
   const void* tp = teacher.has_value() ? teacher->data_ptr() : nullptr;
   const int tdt = teacher.has_value() ? dt(*teacher) : 0;
   c10::hip::HIPGuard g(logits.device().index());
   auto dl = at::empty_like(logits);
+  if (successive.has_value()) {
+    const at::Tensor& u = *successive;
+    TORCH_CHECK(u.is_cuda() && u.sizes() == logits.sizes() && u.is_contiguous() &&
+                (!teacher.has_value() || teacher->scalar_type() == u.scalar_type()), "head_stats_bwd: successive");
+    as::head_stats2_bwd(logits.data_ptr(), dt(logits), tp, u.data_ptr(), dt(u), action.data_ptr<int64_t>(),
+                        stats.data_ptr<float>(), grad.data_ptr<float>(), dl.data_ptr(), R, static_cast<int>(C),
+                        stream());
+    return dl;
+  }
   as::head_stats_bwd(logits.data_ptr(), dt(logits), tp, tdt, action.data_ptr<int64_t>(), stats.data_ptr<float>(),
                      grad.data_ptr<float>(), dl.data_ptr(), R, static_cast<int>(C), stream());
   return dl;
@@ -2159,10 +2185,15 @@ std::vector<at::Tensor> gate_chain_f32(const at::Tensor& x, const std::vector<at
 
 // ---------------------------------------------------------------- RL loss tail (rl_loss.hip)
 // -> {info [rl_loss_info_size(F)], dalp, dent, dkl [6,T,B], dv [F,T+1,B]}
+// with sk [6,T,B] and dflag [T,B] (DAPO; sc carries 7 more scalars): info [rl_loss_dapo_info_size(F)] and a sixth
+// result dsk [6,T,B]
 std::vector<at::Tensor> rl_loss(const at::Tensor& alp, const at::Tensor& blp, const at::Tensor& hm, const at::Tensor& ent,
                                 const at::Tensor& kl, const at::Tensor& v, const at::Tensor& r, const at::Tensor& wm,
                                 const at::Tensor& atflag, const at::Tensor& sc, int64_t upgo_f, bool only_value,
-                                bool ordered) {
+                                bool ordered, const c10::optional<at::Tensor>& sk,
+                                const c10::optional<at::Tensor>& dflag) {
+  const bool dapo = sk.has_value();
+  TORCH_CHECK(dapo == dflag.has_value(), "rl_loss: sk and dflag go together");
   for (const at::Tensor* t : {&alp, &blp, &hm, &ent, &kl, &v, &r, &wm, &atflag, &sc}) {
     check_cuda(*t, "rl_loss operand");
     TORCH_CHECK(t->scalar_type() == at::kFloat, "rl_loss: fp32 operands");
@@ -2174,8 +2205,26 @@ std::vector<at::Tensor> rl_loss(const at::Tensor& alp, const at::Tensor& blp, co
   TORCH_CHECK(F >= 1 && F <= 6 && v.dim() == 3 && v.size(1) == T + 1 && v.size(2) == B && r.dim() == 3 &&
               r.size(0) == F && r.size(1) == T && r.size(2) == B && wm.sizes() == r.sizes(), "rl_loss: fields");
   TORCH_CHECK(atflag.numel() == T * B && T * B <= as::rl_loss_max_tb() && T >= 1, "rl_loss: [T,B] size");
-  TORCH_CHECK(sc.numel() == 4 * F + 4 * 6 + 4 && upgo_f >= -1 && upgo_f < F, "rl_loss: scalars");
+  TORCH_CHECK(sc.numel() == 4 * F + 4 * 6 + 4 + (dapo ? 7 : 0) && upgo_f >= -1 && upgo_f < F, "rl_loss: scalars");
   c10::hip::HIPGuard g(alp.device().index());
+  if (dapo) {
+    for (const at::Tensor* t : {&*sk, &*dflag}) {
+      check_cuda(*t, "rl_loss operand");
+      TORCH_CHECK(t->scalar_type() == at::kFloat, "rl_loss: fp32 operands");
+    }
+    TORCH_CHECK(sk->sizes() == alp.sizes() && dflag->numel() == T * B, "rl_loss: sk [6,T,B], dflag [T,B]");
+    auto info = at::empty({as::rl_loss_dapo_info_size(static_cast<int>(F))}, alp.options());
+    auto dalp = at::empty_like(alp), dent = at::empty_like(alp), dkl = at::empty_like(alp), dsk = at::empty_like(alp),
+         dv = at::empty_like(v);
+    as::rl_loss_dapo(alp.data_ptr<float>(), blp.data_ptr<float>(), hm.data_ptr<float>(), ent.data_ptr<float>(),
+                     kl.data_ptr<float>(), v.data_ptr<float>(), r.data_ptr<float>(), wm.data_ptr<float>(),
+                     atflag.data_ptr<float>(), sk->data_ptr<float>(), dflag->data_ptr<float>(), sc.data_ptr<float>(),
+                     static_cast<int>(F), static_cast<int>(T), static_cast<int>(B), static_cast<int>(upgo_f),
+                     only_value ? 1 : 0, ordered, dalp.data_ptr<float>(), dent.data_ptr<float>(),
+                     dkl.data_ptr<float>(), dsk.data_ptr<float>(), dv.data_ptr<float>(), info.data_ptr<float>(),
+                     stream());
+    return {info, dalp, dent, dkl, dv, dsk};
+  }
   auto info = at::empty({as::rl_loss_info_size(static_cast<int>(F))}, alp.options());
   auto dalp = at::empty_like(alp), dent = at::empty_like(alp), dkl = at::empty_like(alp), dv = at::empty_like(v);
   (ordered ? as::rl_loss_ordered : as::rl_loss)(
@@ -2579,7 +2628,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vsp_fwd", &vsp_fwd);
   m.def("rl_loss", &rl_loss, py::arg("alp"), py::arg("blp"), py::arg("hm"), py::arg("ent"), py::arg("kl"), py::arg("v"),
         py::arg("r"), py::arg("wm"), py::arg("atflag"), py::arg("sc"), py::arg("upgo_f"), py::arg("only_value"),
-        py::arg("ordered") = false);
+        py::arg("ordered") = false, py::arg("sk") = py::none(), py::arg("dflag") = py::none());
   m.def("gate_chain", &gate_chain);
   m.def("gate_chain_f32", &gate_chain_f32);
   m.def("vsp_pool_fwd", &vsp_pool_fwd);
@@ -2589,13 +2638,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vsp_bwd", &vsp_bwd);
   m.def("loc_in_supported", [](int64_t c, int64_t p) { return as::loc_in_supported(static_cast<int>(c), static_cast<int>(p)); });
   m.def("loc_in_bwd", &loc_in_bwd);
-  m.def("head_stats_fwd", &head_stats_fwd);
+  m.def("head_stats_fwd", &head_stats_fwd, py::arg("logits"), py::arg("teacher"), py::arg("action"),
+        py::arg("successive") = py::none());
   m.def("resmlp_fwd", &resmlp_fwd);
   m.def("resmlp_bwd", &resmlp_bwd);
   m.def("bo_encoder_fwd", &bo_encoder_fwd);
   m.def("bo_encoder_bwd", &bo_encoder_bwd, py::arg("bo"), py::arg("loc"), py::arg("params"), py::arg("save"),
         py::arg("dmean"), py::arg("ordered") = false);
-  m.def("head_stats_bwd", &head_stats_bwd);
+  m.def("head_stats_bwd", &head_stats_bwd, py::arg("logits"), py::arg("teacher"), py::arg("action"), py::arg("stats"),
+        py::arg("grad"), py::arg("successive") = py::none());
   m.def("act_grad_nhwc", &act_grad_nhwc);
   m.def("conv3x3_supported", [](int64_t cin, int64_t cout) { return as::conv3x3_supported(static_cast<int>(cin), static_cast<int>(cout)); });
 }

@@ -517,6 +517,12 @@ void head_stats_fwd(const void* l, int l_dt, const void* t, int t_dt, const long
 // dl [R, C] (l's dtype) = g_a d(logp_a) + g_H dH + g_KL dKL, g [3, R]
 void head_stats_bwd(const void* l, int l_dt, const void* t, int t_dt, const long* act, const float* stats,
                     const float* g, void* dl, long R, int C, hipStream_t s);
+// with a second reference distribution u [R, C] (t may be null; t and u share the storage type tu_dt):
+// out [4, R] = (logp_a, entropy, KL(t || l), KL(u || l)); stats [R, 8]; g [4, R]
+void head_stats2_fwd(const void* l, int l_dt, const void* t, const void* u, int tu_dt, const long* act, float* out,
+                     float* stats, long R, int C, hipStream_t s);
+void head_stats2_bwd(const void* l, int l_dt, const void* t, const void* u, int tu_dt, const long* act,
+                     const float* stats, const float* g, void* dl, long R, int C, hipStream_t s);
 // ---- rl_loss.hip: the RL loss after the per-head statistics, with its closed-form gradients (one workgroup)
 int rl_loss_info_size(int F);
 int rl_loss_max_tb();
@@ -528,6 +534,13 @@ void rl_loss_ordered(const float* alp, const float* blp, const float* hm, const 
                      const float* v, const float* r, const float* wm, const float* atflag, const float* sc, int F, int T,
                      int B, int upgo_f, int only_value, float* dalp, float* dent, float* dkl, float* dv, float* info,
                      hipStream_t s);
+// with the DAPO term: sk [6,T,B] successive KL, dflag [T,B], sc extended by dapo_w[6], w_dapo; dsk [6,T,B];
+// info [rl_loss_dapo_info_size(F)] (dapo/<head> x 6 and dapo/total before the total, which stays last)
+int rl_loss_dapo_info_size(int F);
+void rl_loss_dapo(const float* alp, const float* blp, const float* hm, const float* ent, const float* kl,
+                  const float* v, const float* r, const float* wm, const float* atflag, const float* sk,
+                  const float* dflag, const float* sc, int F, int T, int B, int upgo_f, int only_value, bool ordered,
+                  float* dalp, float* dent, float* dkl, float* dsk, float* dv, float* info, hipStream_t s);
 
 // ---- ordered.hip: order-fixed sums of the deterministic mode (no float atomics; idt codes as embed_relu_fwd)
 // workgroups of table_grad_ordered for U rows (single: one workgroup, the result written outright)

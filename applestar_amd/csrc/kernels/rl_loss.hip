@@ -11,6 +11,9 @@
 // masks); atflag [T, B] (action-type KL gate); sc: per-field / per-head scalars (layout in the kernel; built
 // by ReinforcementLoss._scalars).
 // Outputs: dalp / dent / dkl [6, T, B], dv [F, T+1, B], info [rl_loss_info_size(F)] (total loss last).
+// DAPO form (rl_loss_dapo*): two more inputs, sk [6, T, B] (per-head KL from the successive model, reduced like
+// kl) and dflag [T, B] (step < dapo_steps), seven more scalars (dapo_w[6], w_dapo), one more gradient dsk
+// [6, T, B] and seven more info entries (dapo/<head> x 6, dapo/total) between the critic total and the total.
 // Formulas: rl_utils.py (vtrace_advantages, upgo_returns, lambda_returns, td_lambda_loss), loss.py.
 #include "../common.h"
 #include "../kernels.h"
@@ -27,35 +30,42 @@ __device__ __forceinline__ void lds_add(float* p, float v) { atomicAdd(p, v); }
 
 // DET (the deterministic mode): every sum that lds_add takes in arrival order is taken in a fixed order instead -
 // each lane stages its terms in LDS and one fixed thread per quantity adds them in lane order.
-template <bool DET>
-__global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict__ alp, const float* __restrict__ blp,
-                                                         const float* __restrict__ hm, const float* __restrict__ ent,
-                                                         const float* __restrict__ kl, const float* __restrict__ v,
-                                                         const float* __restrict__ r, const float* __restrict__ wm,
-                                                         const float* __restrict__ atflag,
-                                                         const float* __restrict__ sc, int F, int T, int B, int upgo_f,
-                                                         int only_value, float* __restrict__ dalp,
-                                                         float* __restrict__ dent, float* __restrict__ dkl,
-                                                         float* __restrict__ dv, float* __restrict__ info) {
+template <bool DET, bool DAPO>
+__device__ __forceinline__ void rl_loss_body(const float* __restrict__ alp, const float* __restrict__ blp,
+                                             const float* __restrict__ hm, const float* __restrict__ ent,
+                                             const float* __restrict__ kl, const float* __restrict__ v,
+                                             const float* __restrict__ r, const float* __restrict__ wm,
+                                             const float* __restrict__ atflag, const float* __restrict__ sk,
+                                             const float* __restrict__ dflag, const float* __restrict__ sc, int F,
+                                             int T, int B, int upgo_f, int only_value, float* __restrict__ dalp,
+                                             float* __restrict__ dent, float* __restrict__ dkl,
+                                             float* __restrict__ dsk, float* __restrict__ dv,
+                                             float* __restrict__ info) {
   // scalars: per field f: [w_pg, w_baseline, gamma_pg, gamma_baseline]; then pg_w[6], upgo_w[6], ent_w[6],
-  // kl_w[6], w_upgo, w_entropy, w_kl, w_action_type_kl
+  // kl_w[6], w_upgo, w_entropy, w_kl, w_action_type_kl; DAPO: then dapo_w[6], w_dapo
   const float* fsc = sc;
   const float* pg_w = sc + 4 * F;
   const float* upgo_w = pg_w + kH;
   const float* ent_w = upgo_w + kH;
   const float* kl_w = ent_w + kH;
   const float w_upgo = kl_w[kH], w_ent = kl_w[kH + 1], w_kl = kl_w[kH + 2], w_atkl = kl_w[kH + 3];
+  const float* dapo_w = kl_w + kH + 4;
+  const float w_dapo = DAPO ? dapo_w[kH] : 0.f;
   const int TB = T * B;
   const float inv = 1.f / static_cast<float>(TB);
 
   __shared__ float g_up[kMaxTB];
   // accumulators: pg[f][h], td[f], rew[f], val[f], upgo[h], ent[h], kl[h], atkl
   __shared__ float s_pg[kMaxF][kH], s_td[kMaxF], s_rew[kMaxF], s_val[kMaxF], s_up[kH], s_ent[kH], s_kl[kH], s_at;
-  __shared__ float stage[DET ? 2 * kH + 1 : 1][kLossT];   // per-lane terms of the ordered sums
+  __shared__ float s_dapo[DAPO ? kH : 1];
+  __shared__ float stage[DET ? (DAPO ? 3 : 2) * kH + 1 : 1][kLossT];   // per-lane terms of the ordered sums
   const int tid = threadIdx.x;
   if (tid < kMaxF * kH) s_pg[tid / kH][tid % kH] = 0.f;
   if (tid < kMaxF) { s_td[tid] = 0.f; s_rew[tid] = 0.f; s_val[tid] = 0.f; }
   if (tid < kH) { s_up[tid] = 0.f; s_ent[tid] = 0.f; s_kl[tid] = 0.f; }
+  if constexpr (DAPO) {
+    if (tid < kH) s_dapo[tid] = 0.f;
+  }
   if (tid == 0) s_at = 0.f;
   __syncthreads();
 
@@ -180,9 +190,9 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
   }
 
   // ---- phase C: entropy and KL, elementwise over [6, T, B]
-  float pe[kH], pk[kH], pa = 0.f;
+  float pe[kH], pk[kH], pd[kH], pa = 0.f;
 #pragma unroll
-  for (int h = 0; h < kH; ++h) { pe[h] = 0.f; pk[h] = 0.f; }
+  for (int h = 0; h < kH; ++h) { pe[h] = 0.f; pk[h] = 0.f; pd[h] = 0.f; }
   for (int i = tid; i < kH * TB; i += kLossT) {
     const int h = i / TB, o = i % TB;
     const float m = hm[i];
@@ -199,6 +209,13 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
     }
     dent[i] = only_value ? 0.f : -w_ent * ent_w[h] * m * inv;
     dkl[i] = dk;
+    if constexpr (DAPO) {
+      const float mf = m * dflag[o];
+      const float d = sk[i] * mf;
+#pragma unroll
+      for (int q = 0; q < kH; ++q) pd[q] += q == h ? d : 0.f;
+      dsk[i] = only_value ? 0.f : w_dapo * dapo_w[h] * mf * inv;
+    }
   }
   if constexpr (DET) {
 #pragma unroll
@@ -207,13 +224,18 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
       stage[kH + h][tid] = pk[h];
     }
     stage[2 * kH][tid] = pa;
+    if constexpr (DAPO) {
+#pragma unroll
+      for (int h = 0; h < kH; ++h) stage[2 * kH + 1 + h][tid] = pd[h];
+    }
     __syncthreads();
-    if (tid < 2 * kH + 1) {
+    if (tid < (DAPO ? 3 : 2) * kH + 1) {
       float a = 0.f;
       for (int l = 0; l < kLossT; ++l) a += stage[tid][l];
       if (tid < kH) s_ent[tid] = a;
       else if (tid < 2 * kH) s_kl[tid - kH] = a;
-      else s_at = a;
+      else if (tid == 2 * kH) s_at = a;
+      else s_dapo[tid - 2 * kH - 1] = a;
     }
   } else {
 #pragma unroll
@@ -224,6 +246,13 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
     {
       const float sa = wave_sum(pa);
       if ((tid & 63) == 0) lds_add(&s_at, sa);
+    }
+    if constexpr (DAPO) {
+#pragma unroll
+      for (int h = 0; h < kH; ++h) {
+        const float sd = wave_sum(pd[h]);
+        if ((tid & 63) == 0) lds_add(&s_dapo[h], sd);
+      }
     }
   }
   __syncthreads();
@@ -266,13 +295,51 @@ __global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict
     info[o++] = at;
     info[o++] = critic;
     if (upgo_f < 0) ut = 0.f;
-    info[o] = only_value ? critic : total + ut * w_upgo + critic + et * w_ent + kt * w_kl + at * w_atkl;
+    if constexpr (DAPO) {
+      float dt = 0.f;
+      for (int h = 0; h < kH; ++h) {
+        info[o++] = s_dapo[h] * inv;
+        dt += s_dapo[h] * inv * dapo_w[h];
+      }
+      info[o++] = dt;
+      info[o] = only_value ? critic
+                           : total + ut * w_upgo + critic + et * w_ent + kt * w_kl + at * w_atkl + dt * w_dapo;
+    } else {
+      info[o] = only_value ? critic : total + ut * w_upgo + critic + et * w_ent + kt * w_kl + at * w_atkl;
+    }
   }
+}
+
+template <bool DET>
+__global__ __launch_bounds__(kLossT) void rl_loss_kernel(const float* __restrict__ alp, const float* __restrict__ blp,
+                                                         const float* __restrict__ hm, const float* __restrict__ ent,
+                                                         const float* __restrict__ kl, const float* __restrict__ v,
+                                                         const float* __restrict__ r, const float* __restrict__ wm,
+                                                         const float* __restrict__ atflag,
+                                                         const float* __restrict__ sc, int F, int T, int B, int upgo_f,
+                                                         int only_value, float* __restrict__ dalp,
+                                                         float* __restrict__ dent, float* __restrict__ dkl,
+                                                         float* __restrict__ dv, float* __restrict__ info) {
+  rl_loss_body<DET, false>(alp, blp, hm, ent, kl, v, r, wm, atflag, nullptr, nullptr, sc, F, T, B, upgo_f, only_value,
+                           dalp, dent, dkl, nullptr, dv, info);
+}
+
+template <bool DET>
+__global__ __launch_bounds__(kLossT) void rl_loss_dapo_kernel(
+    const float* __restrict__ alp, const float* __restrict__ blp, const float* __restrict__ hm,
+    const float* __restrict__ ent, const float* __restrict__ kl, const float* __restrict__ v,
+    const float* __restrict__ r, const float* __restrict__ wm, const float* __restrict__ atflag,
+    const float* __restrict__ sk, const float* __restrict__ dflag, const float* __restrict__ sc, int F, int T, int B,
+    int upgo_f, int only_value, float* __restrict__ dalp, float* __restrict__ dent, float* __restrict__ dkl,
+    float* __restrict__ dsk, float* __restrict__ dv, float* __restrict__ info) {
+  rl_loss_body<DET, true>(alp, blp, hm, ent, kl, v, r, wm, atflag, sk, dflag, sc, F, T, B, upgo_f, only_value, dalp,
+                          dent, dkl, dsk, dv, info);
 }
 
 }  // namespace
 
 int rl_loss_info_size(int F) { return 10 * F + 7 + 7 + 8 + 1 + 1; }
+int rl_loss_dapo_info_size(int F) { return rl_loss_info_size(F) + kH + 1; }
 int rl_loss_max_tb() { return kMaxTB; }
 
 void rl_loss(const float* alp, const float* blp, const float* hm, const float* ent, const float* kl, const float* v,
@@ -288,6 +355,19 @@ void rl_loss_ordered(const float* alp, const float* blp, const float* hm, const 
                      hipStream_t s) {
   hipLaunchKernelGGL(rl_loss_kernel<true>, dim3(1), dim3(kLossT), 0, s, alp, blp, hm, ent, kl, v, r, wm, atflag, sc, F,
                      T, B, upgo_f, only_value, dalp, dent, dkl, dv, info);
+}
+
+void rl_loss_dapo(const float* alp, const float* blp, const float* hm, const float* ent, const float* kl,
+                  const float* v, const float* r, const float* wm, const float* atflag, const float* sk,
+                  const float* dflag, const float* sc, int F, int T, int B, int upgo_f, int only_value, bool ordered,
+                  float* dalp, float* dent, float* dkl, float* dsk, float* dv, float* info, hipStream_t s) {
+  if (ordered) {
+    hipLaunchKernelGGL(rl_loss_dapo_kernel<true>, dim3(1), dim3(kLossT), 0, s, alp, blp, hm, ent, kl, v, r, wm, atflag,
+                       sk, dflag, sc, F, T, B, upgo_f, only_value, dalp, dent, dkl, dsk, dv, info);
+  } else {
+    hipLaunchKernelGGL(rl_loss_dapo_kernel<false>, dim3(1), dim3(kLossT), 0, s, alp, blp, hm, ent, kl, v, r, wm,
+                       atflag, sk, dflag, sc, F, T, B, upgo_f, only_value, dalp, dent, dkl, dsk, dv, info);
+  }
 }
 
 }  // namespace as

@@ -9,6 +9,9 @@ Capabilities of ``distar/ctools/worker/league/league.py:30-875``:
 * ``actor_send_result``: queued, applied by a worker thread: payoffs (both sides), ELO, per-race stats;
 * ``learner_send_train_info``: adds trained frames, snapshots the player into a historical player
   when trained enough, and resets it (new checkpoint) when its policy says so;
+* DAPO (``learner.use_dapo``): a lagged copy of every active player's checkpoint (the "successive model") under
+  ``league_models/successive_model/<player_id>/``, refreshed every half phase (``save_successive_model``); jobs
+  carry its path for main players;
 * resume: periodic JSON snapshot of all players / payoffs / ELO (the reference pickles with dill).
 """
 from __future__ import annotations
@@ -134,6 +137,7 @@ class League:
             self.active_players[player_id] = p
         if isinstance(p, MainPlayer) and self.cfg.save_initial_snapshot:
             self.save_snapshot(p)
+        self.save_successive_model(p)
         return True
 
     # ------------------------------------------------------------------ learner side
@@ -155,6 +159,37 @@ class League:
         self.logger.info(f'snapshot {player.player_id} -> {hp.player_id}')
         return hp.player_id
 
+    def save_successive_model(self, player: ActivePlayer) -> None:
+        """DAPO: keep a lagged copy of ``player``'s checkpoint in ``league_models/successive_model/<player_id>/``
+        and point ``player.successive_model_path`` at it (league.py:208-226).  Two files: the served one and the
+        copy made at this save (``.bak``), which becomes the served one at the next save - so the served model
+        lags the player by one save interval (half a phase).  After the very first save the copy just made is
+        served (the reference points at a file that does not exist yet).  No-op unless ``learner.use_dapo``."""
+        if not self.whole_cfg.learner.get('use_dapo', False):
+            return
+        d = os.path.join(self.model_dir, 'successive_model', player.player_id)
+        os.makedirs(d, exist_ok=True)
+        if not os.path.isfile(str(player.checkpoint_path)):
+            return
+        # a fixed name: the learner may report a new checkpoint file name between two saves
+        served = os.path.join(d, f'{player.player_id}_successive.pth.tar')
+        pending = served + '.bak'
+        with self.lock:
+            if os.path.exists(pending):
+                os.replace(pending, served)
+            shutil.copyfile(player.checkpoint_path, pending + '.tmp')
+            os.replace(pending + '.tmp', pending)
+            if not os.path.exists(served):
+                shutil.copyfile(pending, served)
+            player.successive_model_path = served
+            player.last_successive_step = player.total_agent_step
+        self.logger.info(f'successive model of {player.player_id}: {served}')
+
+    def _successive_path(self, p) -> str:
+        if isinstance(p, MainPlayer) and self.whole_cfg.learner.get('use_dapo', False):
+            return p.successive_model_path
+        return 'none'
+
     def learner_send_train_info(self, info: Dict) -> Dict:
         pid = info['player_id']
         p = self.active_players[pid]
@@ -166,6 +201,8 @@ class League:
             k: v for k, v in self.historical_players.items() if v.pipeline != 'bot'}
         reset = p.reset_flag
         new_hp = None
+        if self.whole_cfg.learner.get('use_dapo', False) and p.is_save_successive_model():
+            self.save_successive_model(p)
         if p.is_trained_enough(hist, self.active_players, pfsp_train_bot=self.cfg.pfsp_train_bot):
             new_hp = self.save_snapshot(p)
             reset |= p.is_reset()
@@ -178,6 +215,7 @@ class League:
                 if src and os.path.exists(src) and os.path.abspath(src) != os.path.abspath(p.checkpoint_path):
                     shutil.copyfile(src, p.checkpoint_path)
             self.logger.info(f'reset {pid} from {src}')
+            self.save_successive_model(p)
             return {'reset_checkpoint_path': p.checkpoint_path}
         return {'reset_checkpoint_path': 'none'}
 
@@ -205,6 +243,7 @@ class League:
         lvl = random.choices(range(len(self.cfg.bot_probs)), weights=self.cfg.bot_probs, k=1)[0]
         job = {'player_ids': [p.player_id], 'side_ids': [0], 'checkpoint_paths': [p.checkpoint_path],
                'successive_ids': [p.player_id if isinstance(p, MainPlayer) else 'none'],
+               'successive_checkpoint_paths': [self._successive_path(p)],
                'pipelines': [p.pipeline], 'z_path': [p.z_path], 'z_prob': [p.z_prob],
                'teacher_player_ids': [p.teacher_id], 'teacher_checkpoint_paths': [p.teacher_checkpoint_path],
                'send_data_players': [p.player_id], 'update_players': [p.player_id],
@@ -220,6 +259,7 @@ class League:
         job = {'player_ids': [q.player_id for q in players], 'side_ids': list(range(len(players))),
                'pipelines': [q.pipeline for q in players], 'checkpoint_paths': [q.checkpoint_path for q in players],
                'successive_ids': [q.player_id if isinstance(q, MainPlayer) else 'none' for q in players],
+               'successive_checkpoint_paths': [self._successive_path(q) for q in players],
                'z_path': [q.z_path for q in players], 'z_prob': [q.z_prob for q in players],
                'teacher_player_ids': [q.teacher_id for q in players],
                'teacher_checkpoint_paths': [q.teacher_checkpoint_path for q in players],
@@ -235,6 +275,7 @@ class League:
         elif 'eval' in branch:
             job['teacher_player_ids'] = ['none'] * len(players)
             job['teacher_checkpoint_paths'] = ['none'] * len(players)
+            job['successive_checkpoint_paths'] = ['none'] * len(players)
             job['send_data_players'] = []
         return branch, job
 
@@ -256,7 +297,8 @@ class League:
                 ids.append(pid); paths.append('none'); pipes.append('bot'); zps.append('none'); zpr.append(0.0)
                 fr.append(1)
         job = {'player_ids': ids, 'side_ids': [0, 1], 'pipelines': pipes, 'checkpoint_paths': paths,
-               'successive_ids': ['none', 'none'], 'z_path': zps, 'z_prob': zpr,
+               'successive_ids': ['none', 'none'], 'successive_checkpoint_paths': ['none', 'none'],
+               'z_path': zps, 'z_prob': zpr,
                'teacher_player_ids': ['none', 'none'], 'teacher_checkpoint_paths': ['none', 'none'],
                'send_data_players': [], 'update_players': [], 'frac_ids': fr,
                'env_info': {'player_ids': ids, 'side_id': [0, 1]}}
@@ -346,6 +388,8 @@ class League:
             self.elo = ELORating.from_dict(d['elo'])
             if 'trueskill' in d:
                 self.trueskill = TrueSkillRating.from_dict(d['trueskill'])
+        for p in list(self.active_players.values()):
+            self.save_successive_model(p)
 
     # ------------------------------------------------------------------ admin (league_api.py:56-305)
     def correspondent_player_ids(self, player_id):

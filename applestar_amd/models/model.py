@@ -392,8 +392,10 @@ class Model(nn.Module):
     # ------------------------------------------------------------------ learners
     def rl_learner_forward(self, spatial_info, entity_info, scalar_info, entity_num, hidden_state, action_info,
                            selected_units_num, batch_size: int, unroll_len: int, behaviour_logp=None,
-                           teacher_logit=None, mask=None, reward=None, step=None, value_feature=None, **kwargs):
-        """Observations are flattened time-major: index t*B + b for t in [0, T] (T+1 steps)."""
+                           teacher_logit=None, mask=None, reward=None, step=None, value_feature=None,
+                           successive_logit=None, **kwargs):
+        """Observations are flattened time-major: index t*B + b for t in [0, T] (T+1 steps).
+        ``successive_logit`` (DAPO) passes through to the output, which carries the key only when it is given."""
         B, T = batch_size, unroll_len
         flat_action = {k: v.flatten(0, 1) for k, v in action_info.items()}
         flat_su_num = selected_units_num.flatten(0, 1)
@@ -465,10 +467,13 @@ class Model(nn.Module):
             logits[k] = logits[k].view(T, B, *logits[k].shape[1:])
         su = logits['selected_units']
         logits['selected_units'] = F.pad(su, (0, 0, 0, MAX_SELECTED_UNITS_NUM - su.shape[2]), value=NEG)
-        return {'unroll_len': T, 'batch_size': B, 'selected_units_num': selected_units_num,
-                'target_logit': logits, 'value': values, 'action_log_prob': behaviour_logp,
-                'teacher_logit': teacher_logit, 'mask': mask, 'action': action_info, 'reward': reward,
-                'step': step}
+        out = {'unroll_len': T, 'batch_size': B, 'selected_units_num': selected_units_num,
+               'target_logit': logits, 'value': values, 'action_log_prob': behaviour_logp,
+               'teacher_logit': teacher_logit, 'mask': mask, 'action': action_info, 'reward': reward,
+               'step': step}
+        if successive_logit is not None:
+            out['successive_logit'] = successive_logit
+        return out
 
     def sl_train(self, spatial_info, entity_info, scalar_info, entity_num, selected_units_num, traj_lens,
                  hidden_state, action_info, **kwargs):

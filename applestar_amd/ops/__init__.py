@@ -98,9 +98,10 @@ def value_spatial_proj(sc, own, enemy, w, b):
     return None
 
 
-def rl_loss_tail(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value):
-    """Fused RL loss tail (GPU): (total, info vector); callers check _native(...).has('rl_loss') first."""
-    return _native(v).rl_loss_tail(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value)
+def rl_loss_tail(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value, sk=None, dflag=None):
+    """Fused RL loss tail (GPU): (total, info vector); callers check _native(...).has('rl_loss') first.
+    ``sk`` [6, T, B] / ``dflag`` [T, B] add the DAPO term (``sc`` then carries dapo_w[6], w_dapo at its end)."""
+    return _native(v).rl_loss_tail(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value, sk, dflag)
 
 
 def value_spatial_proj_pool(sc, own, enemy, w, b):
@@ -201,12 +202,17 @@ def action_logp(logits, actions):
     return out
 
 
-def head_stats(logits, teacher, actions):
-    """(logp(action), entropy, KL(teacher || logits)) per distribution row, fp32 (K19 fused kernel on GPU)."""
+def head_stats(logits, teacher, actions, successive=None):
+    """(logp(action), entropy, KL(teacher || logits)) per distribution row, fp32 (K19 fused kernel on GPU).
+    With ``successive`` logits a fourth result, KL(successive || logits), from the same launch."""
     n = _native(logits)
     if n is not None and n.has('head_stats'):
-        return n.head_stats(logits, teacher, actions)
-    return ref.head_stats(logits, teacher, actions)
+        if successive is None:
+            return n.head_stats(logits, teacher, actions)
+        return n.head_stats(logits, teacher, actions, successive)
+    if successive is None:
+        return ref.head_stats(logits, teacher, actions)
+    return ref.head_stats(logits, teacher, actions, successive)
 
 
 def scatter_connection(proj, x, y, H: int, W: int):

@@ -493,28 +493,43 @@ def spatial_embed_pool(spatial_info, rows, entity_x, entity_y, entity_num, w_den
 class _RLLossTail(torch.autograd.Function):
     """The RL loss after the per-head statistics (rl_loss.hip): one kernel computes the total, the info
     vector and the closed-form gradients w.r.t. the stacked log-probs / entropies / KLs / values; backward
-    only scales them by the incoming gradient."""
+    only scales them by the incoming gradient.  With ``sk`` / ``dflag`` (the DAPO term: per-head KL from the
+    successive model and its step gate, ``sc`` extended by dapo_w[6], w_dapo) the info vector carries seven more
+    entries before the total and backward returns a fifth gradient, the one of ``sk``."""
 
     @staticmethod
-    def forward(ctx, alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value):
+    def forward(ctx, alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value, sk=None, dflag=None):
         c = lambda t: t.detach().float().contiguous()  # noqa: E731
-        info, dalp, dent, dkl, dv = _C.rl_loss(c(alp), c(blp), c(hm), c(ent), c(kl), c(v), c(r), c(wm), c(atflag),
-                                               sc, int(upgo_f), bool(only_value), _DETERMINISTIC)
-        ctx.save_for_backward(dalp, dent, dkl, dv)
-        ctx.dtypes = (alp.dtype, ent.dtype, kl.dtype, v.dtype)
+        ctx.dapo = sk is not None
+        if ctx.dapo:
+            info, dalp, dent, dkl, dv, dsk = _C.rl_loss(c(alp), c(blp), c(hm), c(ent), c(kl), c(v), c(r), c(wm),
+                                                        c(atflag), sc, int(upgo_f), bool(only_value), _DETERMINISTIC,
+                                                        c(sk), c(dflag))
+            ctx.save_for_backward(dalp, dent, dkl, dv, dsk)
+            ctx.dtypes = (alp.dtype, ent.dtype, kl.dtype, v.dtype, sk.dtype)
+        else:
+            info, dalp, dent, dkl, dv = _C.rl_loss(c(alp), c(blp), c(hm), c(ent), c(kl), c(v), c(r), c(wm), c(atflag),
+                                                   sc, int(upgo_f), bool(only_value), _DETERMINISTIC)
+            ctx.save_for_backward(dalp, dent, dkl, dv)
+            ctx.dtypes = (alp.dtype, ent.dtype, kl.dtype, v.dtype)
         ctx.mark_non_differentiable(info)
         return info[-1], info
 
     @staticmethod
     def backward(ctx, gtotal, ginfo):
+        if ctx.dapo:
+            grads = tuple((g * gtotal).to(dt) for g, dt in zip(ctx.saved_tensors, ctx.dtypes))
+            return grads[:4] + (None,) * 8 + (grads[4], None)
         dalp, dent, dkl, dv = ctx.saved_tensors
         da, de, dk, dvv = (g * gtotal for g in (dalp, dent, dkl, dv))
-        return (da.to(ctx.dtypes[0]), de.to(ctx.dtypes[1]), dk.to(ctx.dtypes[2]), dvv.to(ctx.dtypes[3])) + (None,) * 8
+        return (da.to(ctx.dtypes[0]), de.to(ctx.dtypes[1]), dk.to(ctx.dtypes[2]), dvv.to(ctx.dtypes[3])) + (None,) * 10
 
 
-def rl_loss_tail(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value):
+def rl_loss_tail(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value, sk=None, dflag=None):
     """(total loss 0-d, info vector) of the fused RL loss tail; see rl/loss.py _compute_loss_fused."""
-    return _RLLossTail.apply(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value)
+    if sk is None:
+        return _RLLossTail.apply(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value)
+    return _RLLossTail.apply(alp, ent, kl, v, blp, hm, r, wm, atflag, sc, upgo_f, only_value, sk, dflag)
 
 
 # ---------------------------------------------------------------------------- varlen attention
@@ -2488,8 +2503,29 @@ class _HeadStats(torch.autograd.Function):
         return _C.head_stats_bwd(logits, teacher, action, stats, g), None, None
 
 
-def head_stats(logits, teacher, actions):
-    """Fused ``reference.head_stats`` for fp32 / bf16 logits [..., C]."""
+class _HeadStats2(torch.autograd.Function):
+    """(logp_a, entropy, KL, KL from the successive model) per row in one kernel; backward one pass."""
+
+    @staticmethod
+    def forward(ctx, logits, teacher, action, successive):
+        out, stats = _C.head_stats_fwd(logits, teacher, action, successive)
+        ctx.save_for_backward(logits, teacher, action, stats, successive)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1], out[2], out[3]
+
+    @staticmethod
+    def backward(ctx, ga, gh, gk, gu):
+        logits, teacher, action, stats, successive = ctx.saved_tensors
+        R = logits.shape[0]
+        z = logits.new_zeros(R, dtype=torch.float32)
+        g = torch.stack([z if x is None else x.float() for x in (ga, gh, gk, gu)]).contiguous()
+        return _C.head_stats_bwd(logits, teacher, action, stats, g, successive), None, None, None
+
+
+def head_stats(logits, teacher, actions, successive=None):
+    """Fused ``reference.head_stats`` for fp32 / bf16 logits [..., C].  The kernels read the teacher and the
+    successive logits as one storage type: with both given, the successive tensor is converted to the teacher's
+    dtype (fp32 or bf16) first; without a teacher it keeps its own."""
     C = logits.shape[-1]
     lead = logits.shape[:-1]
     l2 = logits if logits.dtype in (torch.float32, torch.bfloat16) else logits.float()
@@ -2499,6 +2535,14 @@ def head_stats(logits, teacher, actions):
         t2 = teacher.detach()
         t2 = (t2 if t2.dtype in (torch.float32, torch.bfloat16) else t2.float()).reshape(-1, C).contiguous()
     a = actions.reshape(-1).long().contiguous()
+    if successive is not None:
+        u2 = successive.detach()
+        ud = u2.dtype if u2.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        if t2 is not None:
+            ud = t2.dtype
+        u2 = u2.to(ud).reshape(-1, C).contiguous()
+        logp_a, ent, kl, klu = _HeadStats2.apply(l2, t2, a, u2)
+        return logp_a.view(lead), ent.view(lead), kl.view(lead), klu.view(lead)
     logp_a, ent, kl = _HeadStats.apply(l2, t2, a)
     return logp_a.view(lead), ent.view(lead), kl.view(lead)
 

@@ -169,18 +169,24 @@ def categorical_stats(logits: torch.Tensor, actions: torch.Tensor):
     return logp, a_logp
 
 
-def head_stats(logits: torch.Tensor, teacher: Optional[torch.Tensor], actions: torch.Tensor):
+def head_stats(logits: torch.Tensor, teacher: Optional[torch.Tensor], actions: torch.Tensor,
+               successive: Optional[torch.Tensor] = None):
     """Per row of ``logits [..., C]``: (logp(action), entropy, KL(softmax(teacher) || softmax(logits))),
-    fp32, shaped like ``actions`` (rl_loss.py:63-90, as_rl_utils.py:52-127).  KL is 0 without a teacher."""
+    fp32, shaped like ``actions`` (rl_loss.py:63-90, as_rl_utils.py:52-127).  KL is 0 without a teacher.
+    With ``successive [..., C]`` a fourth result: KL(softmax(successive) || softmax(logits)) (DAPO)."""
     lp = torch.log_softmax(logits.float(), dim=-1)
     a = actions.long().clamp(0, logits.shape[-1] - 1)
     logp_a = lp.gather(-1, a.unsqueeze(-1)).squeeze(-1)
     ent = -(lp.exp() * lp).sum(-1)
     if teacher is None:
-        return logp_a, ent, torch.zeros_like(ent)
-    tlp = torch.log_softmax(teacher.float(), dim=-1)
-    kl = (tlp.exp() * (tlp - lp)).sum(-1)
-    return logp_a, ent, kl
+        kl = torch.zeros_like(ent)
+    else:
+        tlp = torch.log_softmax(teacher.float(), dim=-1)
+        kl = (tlp.exp() * (tlp - lp)).sum(-1)
+    if successive is None:
+        return logp_a, ent, kl
+    ulp = torch.log_softmax(successive.float(), dim=-1)
+    return logp_a, ent, kl, (ulp.exp() * (ulp - lp)).sum(-1)
 
 
 def vtrace_advantages(clipped_rhos, clipped_cs, rewards, values, gamma: float = 1.0, lambda_: float = 1.0):

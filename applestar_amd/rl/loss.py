@@ -9,7 +9,11 @@ Differences by design (not in the math):
   gather / product / sum chains over the [T, B, C] logits of both the learner and the teacher;
 * the six heads' V-trace (and UPGO) scans run as one batched reverse scan;
 * nothing calls ``.item()`` — the info dict holds 0-d device tensors that the logger fetches with a
-  single device->host copy (the reference syncs ~40 times per iteration).
+  single device->host copy (the reference syncs ~40 times per iteration);
+* DAPO (KL from the successive model, main players only, gated by ``step < dapo_steps``) is on when
+  ``use_dapo`` is set and the batch carries ``successive_logit``.  Its per-head means are logged as
+  ``dapo/<head>`` and their head-weighted sum (before ``loss_weights.dapo``) as ``dapo/total``; the reference
+  logs them under ``battle/<head>``, which clobbers the battle baseline's keys.
 """
 from __future__ import annotations
 
@@ -84,11 +88,14 @@ class ReinforcementLoss:
     # ------------------------------------------------------------------ fused GPU tail (rl_loss.hip)
     _PG_MASKED_FIELDS = ('build_order', 'built_unit', 'effect')
 
+    def _dapo_on(self, inputs: Dict) -> bool:
+        return self.use_dapo and inputs.get('successive_logit') is not None
+
     def _fused_ok(self, inputs: Dict) -> bool:
         if not FUSED_LOSS:
             return False
         v0 = next(iter(inputs['value'].values()))
-        if not v0.is_cuda or (self.use_dapo and 'successive_logit' in inputs):
+        if not v0.is_cuda:
             return False
         n = ops._native(v0)
         if n is None or not n.has('rl_loss'):
@@ -96,9 +103,9 @@ class ReinforcementLoss:
         T, B = inputs['reward']['winloss'].shape if 'winloss' in inputs['reward'] else (0, 0)
         return 0 < T * B <= 2048 and 1 <= len(inputs['value']) <= 6
 
-    def _scalars(self, fields, device) -> torch.Tensor:
+    def _scalars(self, fields, device, dapo: bool = False) -> torch.Tensor:
         cache = self.__dict__.setdefault('_sc_cache', {})
-        key = (tuple(fields), str(device))
+        key = (tuple(fields), str(device), 'dapo') if dapo else (tuple(fields), str(device))
         if key not in cache:
             c = self.cfg
             vals = []
@@ -108,6 +115,8 @@ class ReinforcementLoss:
             for table in (c.pg_head_weights, c.upgo_head_weights, c.entropy_head_weights, c.kl_head_weights):
                 vals += [table.get(h, 1.0) for h in HEADS]
             vals += [self.w.upgo.winloss, self.w.entropy, self.w.kl, self.w.action_type_kl]
+            if dapo:
+                vals += [c.dapo_head_weights.get(h, 1.0) for h in HEADS] + [self.w.dapo]
             cache[key] = torch.tensor(vals, dtype=torch.float32, device=device)
         return cache[key]
 
@@ -127,9 +136,15 @@ class ReinforcementLoss:
         V = torch.stack([values[k].float() for k in fields], 0)                     # [F, T+1, B]
         not_done = (rewards['winloss'][-1] == 0).to(V.dtype)
         V = torch.cat([V[:, :-1], V[:, -1:] * not_done], 1)
-        alps, blps, ents, kls = [], [], [], []
+        dapo = self._dapo_on(inputs)
+        alps, blps, ents, kls, sks = [], [], [], [], []
         for h in HEADS:
-            alp, ent, kl = ops.head_stats(logits[h], teacher_logits.get(h), actions[h])
+            if dapo:
+                alp, ent, kl, sk = ops.head_stats(logits[h], teacher_logits.get(h), actions[h],
+                                                  inputs['successive_logit'][h])
+                sks.append((sk * su_mask).sum(-1) if h == 'selected_units' else sk)
+            else:
+                alp, ent, kl = ops.head_stats(logits[h], teacher_logits.get(h), actions[h])
             blp = behaviour_logp[h].float()
             if h == 'selected_units':
                 n_valid = masks['selected_units_logits_mask'].float().sum(-1)
@@ -152,9 +167,16 @@ class ReinforcementLoss:
         WM = torch.stack([masks[k + '_mask'].float() if k in self._PG_MASKED_FIELDS else ones for k in fields], 0)
         atflag = (inputs['step'] < self.action_type_kl_steps).float() * masks['cum_action_mask'].float()
         upgo_f = fields.index('winloss') if 'winloss' in fields else -1
-        total, vec = ops.rl_loss_tail(torch.stack(alps, 0), torch.stack(ents, 0), torch.stack(kls, 0), V,
-                                      torch.stack(blps, 0).detach(), hm, R, WM, atflag,
-                                      self._scalars(fields, V.device), upgo_f, self.only_update_value)
+        if dapo:
+            dflag = (inputs['step'] < self.dapo_steps).float()
+            total, vec = ops.rl_loss_tail(torch.stack(alps, 0), torch.stack(ents, 0), torch.stack(kls, 0), V,
+                                          torch.stack(blps, 0).detach(), hm, R, WM, atflag,
+                                          self._scalars(fields, V.device, dapo=True), upgo_f, self.only_update_value,
+                                          torch.stack(sks, 0), dflag)
+        else:
+            total, vec = ops.rl_loss_tail(torch.stack(alps, 0), torch.stack(ents, 0), torch.stack(kls, 0), V,
+                                          torch.stack(blps, 0).detach(), hm, R, WM, atflag,
+                                          self._scalars(fields, V.device), upgo_f, self.only_update_value)
         info: Dict[str, torch.Tensor] = {}
         o = 0
         for f in fields:
@@ -171,6 +193,11 @@ class ReinforcementLoss:
             info[f'{name}/total'] = vec[o + 6]
             o += 7
         info['kl/extra_at'] = vec[o]
+        if dapo:
+            o += 2                                                                  # extra_at, critic total
+            for i, h in enumerate(HEADS):
+                info['dapo/' + h] = vec[o + i]
+            info['dapo/total'] = vec[o + 6]
         info['total_loss'] = total
         return info
 
@@ -297,7 +324,7 @@ class ReinforcementLoss:
 
         # ---------------- DAPO (distillation from a successive model), only for main players
         total_dapo = 0.0
-        if self.use_dapo and 'successive_logit' in inputs:
+        if self._dapo_on(inputs):
             flag = (game_steps < self.dapo_steps).float()
             for h in HEADS:
                 _, _, kl = ops.head_stats(logits[h], inputs['successive_logit'][h], actions[h])
@@ -308,6 +335,7 @@ class ReinforcementLoss:
                 d = (kl * flag).mean()
                 info['dapo/' + h] = d.detach()
                 total_dapo = total_dapo + d * self.cfg.dapo_head_weights.get(h, 1.0)
+            info['dapo/total'] = total_dapo.detach()
             total_dapo = total_dapo * self.w.dapo
 
         if self.only_update_value:

@@ -29,7 +29,9 @@ def _tree_to(x, device, non_blocking=False):
 
 def rl_batch(batch_size: int, unroll_len: int, max_entities: int = MAX_ENTITY_NUM, seed: int = 0,
              use_value_feature: bool = True, baselines=('winloss',), hidden_size: int = 384,
-             num_layers: int = 3, entity_num: Optional[torch.Tensor] = None) -> Dict:
+             num_layers: int = 3, entity_num: Optional[torch.Tensor] = None, successive: bool = False) -> Dict:
+    """``successive``: add ``successive_logit`` (DAPO), shaped and masked like ``teacher_logit``, drawn from a
+    generator of its own so that every other field is the same as without it."""
     g = torch.Generator().manual_seed(seed)
     B, T = batch_size, unroll_len
     n_obs = (T + 1) * B
@@ -97,6 +99,12 @@ def rl_batch(batch_size: int, unroll_len: int, max_entities: int = MAX_ENTITY_NU
         'unroll_len': T,
         'model_last_iter': torch.zeros(B),
     })
+    if successive:
+        g2 = torch.Generator().manual_seed(seed + 0x5CC)
+        succ = {k: torch.randn(v.shape, generator=g2) for k, v in teacher.items()}
+        succ['target_unit'] = succ['target_unit'].masked_fill(~tu_valid, -1e9)
+        succ['selected_units'] = succ['selected_units'].masked_fill(~su_valid | prev_excl | end0, -1e9)
+        batch['successive_logit'] = succ
     return batch
 
 
