@@ -2539,6 +2539,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mask") = py::none(), py::arg("act") = 0);
   m.def("conv_halo_f32_mode", &as::conv_halo_f32_mode);
   m.def("set_conv_halo_f32_mode", &as::set_conv_halo_f32_mode);
+  m.def("conv_wgrad_halo_f32_mode", &as::conv_wgrad_halo_f32_mode);
+  m.def("set_conv_wgrad_halo_f32_mode", &as::set_conv_wgrad_halo_f32_mode);
+  m.def("conv_wgrad_f32_halo_selected", &as::conv_wgrad_f32_halo_selected, py::arg("cout"), py::arg("h"), py::arg("w"),
+        py::arg("cin"));
   m.def("gemm_f32_psb", &gemm_f32_psb, py::arg("a"), py::arg("bsplit"), py::arg("N"), py::arg("K"),
         py::arg("bias") = py::none(), py::arg("res") = py::none(), py::arg("act") = 0, py::arg("variant") = 0);
   m.def("entity_pack", &entity_pack);

@@ -1,5 +1,5 @@
 // The implicit im2col of the 3 x 3 / pad 1 convolutions (conv3x3.hip, conv3x3_f32.hip, conv3x3_f32_v2.hip,
-// conv3x3_f32_halo.hip, gemm_f32_psb.hip): which taps of an output pixel lie inside its image, and where a
+// conv3x3_f32_halo.hip, conv_wgrad_f32_halo.hip, gemm_f32_psb.hip): which taps of an output pixel lie inside its image, and where a
 // K-step's activation piece starts.  The one place that decides whether a neighbouring image's pixels can enter a
 // tile.  K = 9 Cin is tap-major: k = tap Cin + c, tap = 3 (dy + 1) + (dx + 1).
 #pragma once
@@ -7,19 +7,23 @@
 
 namespace as {
 
-// bit t: tap t of output pixel m (of M = B HW pixels, NHWC) reads a pixel of m's own image; 0 for m >= M
-__device__ __forceinline__ int conv_tap_mask(long m, long M, int HW, int H, int W) {
+// bit t: tap t of the pixel at (yy, xx) of an H x W image reads a pixel of that image
+__device__ __forceinline__ int conv_tap_mask_yx(int yy, int xx, int H, int W) {
   int ok = 0;
-  if (m < M) {
-    const int rem = static_cast<int>(m % HW);
-    const int yy = rem / W, xx = rem - yy * W;
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
-      ok |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
-    }
+  for (int t = 0; t < 9; ++t) {
+    const int y2 = yy + t / 3 - 1, x2 = xx + t % 3 - 1;
+    ok |= (y2 >= 0 && y2 < H && x2 >= 0 && x2 < W) << t;
   }
   return ok;
+}
+
+// bit t: tap t of output pixel m (of M = B HW pixels, NHWC) reads a pixel of m's own image; 0 for m >= M
+__device__ __forceinline__ int conv_tap_mask(long m, long M, int HW, int H, int W) {
+  if (m >= M) return 0;
+  const int rem = static_cast<int>(m % HW);
+  const int yy = rem / W;
+  return conv_tap_mask_yx(yy, rem - yy * W, H, W);
 }
 
 // the K-step that starts at k0 (inside one tap): its tap, first channel and the tap's pixel shift dy W + dx

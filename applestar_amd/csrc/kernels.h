@@ -35,7 +35,7 @@ void layer_norm_bwd(const void* dy, int dy_dt, const void* xin, int xin_dt, cons
                     const float* w, const float* mean, const float* rstd, void* dx, int dx_dt,
                     float* dw_part, float* db_part, long rows, int cols, int act, int nblk, hipStream_t s,
                     const float* msrc = nullptr, float* dxm = nullptr);
-void column_reduce(const float* part, float* out, int nrows, int cols, hipStream_t s);
+void column_reduce(float* part, float* out, int nrows, int cols, hipStream_t s);
 // entity packing tables (valid [B][N], packed -> padded row flat[total], segment seg[total], offsets cu[B + 1])
 void entity_pack(const void* num, bool num64, int B, int N, long total, bool* valid, int64_t* flat, int64_t* seg,
                  int* cu, hipStream_t s);
@@ -286,6 +286,16 @@ void gemm_f32(const float* a, const float* b, const float* bias, const float* re
 // slice s writes dW at part + s * part_stride ([N][K]) and db at db_part + s * part_stride ([N])
 void wgrad_f32(const float* dy, const float* x, float* dw_part, float* db_part, long part_stride, long R, int N, int K,
                int H, int W, int Cin, int S, hipStream_t st);
+// conv_wgrad_f32_halo.hip: the 3x3 conv weight gradient with every dY row and input pixel of a slice staged and
+// split once for all nine taps (split-MFMA mode, W <= 80, Cin % 16, 128-multiples of outputs); same partials as
+// wgrad_f32, which sends a conv there when conv_wgrad_f32_halo_selected.  conv_wgrad_halo_f32_mode
+// (APPLESTAR_CONV_WGRAD_HALO_F32): bits 1 = 32, 2 = 64, 4 = 128-multiples of outputs; default 4; 0 = never
+int conv_wgrad_halo_f32_mode();
+void set_conv_wgrad_halo_f32_mode(int mode);
+bool conv_wgrad_f32_halo_supported(int N, int H, int W, int Cin);
+bool conv_wgrad_f32_halo_selected(int N, int H, int W, int Cin);
+void conv_wgrad_f32_halo(const float* dy, const float* x, float* dw_part, float* db_part, long part_stride, long R,
+                         int N, int K, int H, int W, int Cin, int S, long rows_per_split, hipStream_t st);
 
 // ---- heads.hip: fused sampling tails of the action heads (inference) -----------------------------------
 void head_sample(const void* logits, int logits_dt, long ld_logits, int B, int C, float inv_t, const uint8_t* mask,

@@ -617,15 +617,15 @@ void entity_pack(const void* num, bool num64, int B, int N, long total, bool* va
 }
 
 // part is scratch: a long reduction (> 1024 rows) overwrites the first row of every 256-row chunk
-void column_reduce(const float* part, float* out, int nrows, int cols, hipStream_t s) {
+void column_reduce(float* part, float* out, int nrows, int cols, hipStream_t s) {
   if (nrows <= 1024) {
     hipLaunchKernelGGL(column_reduce_kernel<float>, dim3((cols + 63) / 64), dim3(1024), 0, s, part, out, nrows, cols,
                        static_cast<long>(cols));
     return;
   }
   const int nchunk = (nrows + 255) / 256;
-  hipLaunchKernelGGL(column_reduce_chunk_kernel, dim3((cols + 63) / 64, nchunk), dim3(256), 0, s,
-                     const_cast<float*>(part), nrows, cols);
+  hipLaunchKernelGGL(column_reduce_chunk_kernel, dim3((cols + 63) / 64, nchunk), dim3(256), 0, s, part, nrows,
+                     cols);
   hipLaunchKernelGGL(column_reduce_kernel<float>, dim3((cols + 63) / 64), dim3(1024), 0, s, part, out, nchunk, cols,
                      256L * cols);
 }
