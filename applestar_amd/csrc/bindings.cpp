@@ -1622,7 +1622,9 @@ std::vector<at::Tensor> wgrad_f32(const at::Tensor& dy, const at::Tensor& x, int
     }
     return {at::zeros({N, K}, opts), want_bias ? at::zeros({N}, opts) : at::Tensor()};
   }
-  const int S = as::wgrad_f32_splits(R, static_cast<int>(N), static_cast<int>(K));
+  const int S = cin > 0 ? as::conv_wgrad_f32_splits(R, static_cast<int>(N), static_cast<int>(K), static_cast<int>(H),
+                                                    static_cast<int>(W), static_cast<int>(cin))
+                        : as::wgrad_f32_splits(R, static_cast<int>(N), static_cast<int>(K));
   auto part = (S == 1 && flat.defined()) ? flat.view({1, stride}) : at::empty({S, stride}, opts);
   as::wgrad_f32(dy.data_ptr<float>(), x.data_ptr<float>(), part.data_ptr<float>(),
                 want_bias ? part.data_ptr<float>() + NK : nullptr, stride, R, static_cast<int>(N), static_cast<int>(K),

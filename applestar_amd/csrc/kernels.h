@@ -287,13 +287,15 @@ void gemm_f32(const float* a, const float* b, const float* bias, const float* re
 void wgrad_f32(const float* dy, const float* x, float* dw_part, float* db_part, long part_stride, long R, int N, int K,
                int H, int W, int Cin, int S, hipStream_t st);
 // conv_wgrad_f32_halo.hip: the 3x3 conv weight gradient with every dY row and input pixel of a slice staged and
-// split once for all nine taps (split-MFMA mode, W <= 80, Cin % 16, 128-multiples of outputs); same partials as
-// wgrad_f32, which sends a conv there when conv_wgrad_f32_halo_selected.  conv_wgrad_halo_f32_mode
-// (APPLESTAR_CONV_WGRAD_HALO_F32): bits 1 = 32, 2 = 64, 4 = 128-multiples of outputs; default 4; 0 = never
+// split once for all nine taps (split-MFMA mode, W <= 80, Cin % 16, 128-multiples of outputs or at most 64); same
+// partials as wgrad_f32, which sends a conv there when conv_wgrad_f32_halo_selected.  conv_wgrad_halo_f32_mode
+// (APPLESTAR_CONV_WGRAD_HALO_F32): bits 1 = at most 32, 2 = 33 .. 64, 4 = 128-multiples of outputs; 0 = never.
+// conv_wgrad_f32_splits: the slice count S of a conv (wgrad_f32_splits unless a narrow class goes to the halo kernel)
 int conv_wgrad_halo_f32_mode();
 void set_conv_wgrad_halo_f32_mode(int mode);
 bool conv_wgrad_f32_halo_supported(int N, int H, int W, int Cin);
 bool conv_wgrad_f32_halo_selected(int N, int H, int W, int Cin);
+int conv_wgrad_f32_splits(long R, int N, int K, int H, int W, int Cin);
 void conv_wgrad_f32_halo(const float* dy, const float* x, float* dw_part, float* db_part, long part_stride, long R,
                          int N, int K, int H, int W, int Cin, int S, long rows_per_split, hipStream_t st);
 

@@ -33,7 +33,11 @@
 // number of tiles.  Summation order: fixed (stage by stage, no atomics); a stage holds the same 16 rows as in the
 // split-once kernel of wgrad_f32.hip and db is summed in that kernel's order, so both results have its bits.
 //
-// This file: the kernel, its launcher, the support predicate and the switch (conv_wgrad_halo_f32_mode).
+// At most 64 outputs cannot fill four waves along the outputs: conv_wgrad_f32_halo_narrow_kernel below puts the
+// waves along the reduction rows instead (its budget and order are written there) and has its own slice count.
+//
+// This file: the two kernels, their launchers, the support predicate, the slice count of a conv
+// (conv_wgrad_f32_splits) and the switch (conv_wgrad_halo_f32_mode).
 #include <cstdlib>
 
 #include "../common.h"
@@ -293,12 +297,282 @@ void launch_wg_halo(const float* dy, const float* x, float* dwp, float* dbp, lon
                      dwp, dbp, ps, R, N, K, H, W, Cin, rps, tiles_n, chunks);
 }
 
-// APPLESTAR_CONV_WGRAD_HALO_F32 / set_conv_wgrad_halo_f32_mode: bits 1 = 32, 2 = 64, 4 = 128-multiples of outputs;
-// 0 = the kernels of wgrad_f32.hip for every conv.  Default 4: the measured choice (docs/PERF_LOG.md)
+// ---- at most 64 outputs: the waves along the reduction rows -------------------------------------------------
+// WN = 1 (N <= 32) or 2 (N <= 64) waves along the outputs, WR = 4 / WN along the rows of a stage of RS = 16 WR
+// pixels: wave (wn, wr) multiplies rows 16 wr .. + 15 of every stage into its own nine 32 x 32 accumulators for
+// outputs 32 wn .., so per stage and wave the work is that of the kernel above (one dY fragment, nine X fragments,
+// 54 MFMAs) and a workgroup again owns all nine taps of a 32-channel chunk - of all outputs.  At the end of the
+// slice the WR copies are added through the LDS in the order wr = 0, 1, .. (no atomics: the order is fixed).
+// A stage of 64 rows with the incoming stage beside the window would need a ring of 2 RS + 2 W + 2 = 290 rows at
+// W = 80, i.e. 512: 98 KB.  So nothing is double-buffered here: the next stage's rows are stored after a second
+// barrier, over the rows the window has just left (ring >= RS + 2 W + 2 = 226 -> 256 rows); its global loads are
+// still issued before the stage's MFMAs.  Two barriers per 64 or 32 rows are no more than the one per 16 above.
+//   LDS   WN = 1: dY 3 x 64 x 64 B = 12.0 KB, X 3 x 257 x 64 B = 48.2 KB: 60.2 KB
+//         WN = 2: dY 3 x 32 x 192 B = 18.0 KB, X 48.2 KB: 66.2 KB            (two workgroups per CU: <= 80 KB)
+//   VGPR  144 accumulators + 36 fragments (dY, two taps of X) + 16 staged floats + addressing: 2 waves per SIMD
+// -Rpass-analysis=kernel-resource-usage: WN = 1 238 VGPRs, 61,632 B of LDS; WN = 2 232 VGPRs, 67,776 B; no AGPRs,
+// no scratch, 2 waves per SIMD (the kernel above: 245 VGPRs, 55,488 / 80,064 B).  db: every thread adds the dY pieces it stages (4
+// columns of 2 rows per stage) to four running sums; the threads of a column are added through the LDS in thread
+// order at the end.  A half-empty tile (16 outputs, 16 channels) runs its MFMAs on zeros.
+template <int WN>
+struct WgNarrowCfg {
+  static constexpr int WR = 4 / WN, RS = 16 * WR, BN = 32 * WN;
+  static constexpr int SA = BN == 32 ? 64 : BN * 2 + 64, SX = kWgCC * 2;         // four rows cover all 64 banks once
+  static constexpr int NRING = 256;
+  static constexpr int PA = RS * SA, PX = (NRING + 1) * SX;
+  static constexpr int SMEM = 3 * PA + 3 * PX;
+  static constexpr int TH = 5;                                                  // taps per pass of the final sum
+  static_assert(RS + 2 * kWgMaxW + 2 <= NRING && 2 * SMEM <= 160 * 1024, "ring size / two workgroups per CU");
+  static_assert(WN * TH * 16 * 64 * 4 <= SMEM && 256 * 4 * 4 <= SMEM, "the final sums reuse the planes");
+};
+
+template <int WN>
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f32_halo_narrow_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ dw_part,
+    float* __restrict__ db_part, long part_stride, long R, int N, int K, int H, int W, int Cin, long rows_per_split,
+    int chunks) {
+  using C = WgNarrowCfg<WN>;
+  constexpr int RS = C::RS, BN = C::BN, CC = kWgCC, SA = C::SA, SX = C::SX, WR = C::WR;
+  constexpr int RINGB = C::NRING * SX;
+  constexpr int AQ = BN / 4, AROWS = 256 / AQ;    // dY pieces: AQ column quads per row, AROWS rows per pass, 2 passes
+  constexpr int XP = RS / 32;                     // X pieces per thread: 8 quads per row, 32 rows per pass
+  static_assert(2 * AROWS == RS, "two dY pieces per thread");
+  __shared__ __attribute__((aligned(16))) char smem[C::SMEM];
+  char* const pa = smem;               // dY planes [plane 3][RS][SA]
+  char* const px = smem + 3 * C::PA;   // X planes [plane 3][NRING + 1][SX]; row NRING is the zero row
+
+  const int wg = pipe::xcd_remap();
+  const int ch = wg % chunks;
+  const int s = wg / chunks;
+  const int c0 = ch * CC;
+  const long r_begin = static_cast<long>(s) * rows_per_split;
+  const long r_end = r_begin + rows_per_split < R ? r_begin + rows_per_split : R;
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wn = wid % WN, wr = wid / WN;
+  const int l32 = lane & 31, h = lane >> 5;
+  const int HW = H * W;
+  const __amdgpu_buffer_rsrc_t yr =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy), 0, static_cast<int>(R * N * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t xr =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, static_cast<int>(R * Cin * 4), 0x00020000);
+  const int nrows = r_end > r_begin ? static_cast<int>(r_end - r_begin) : 0;
+  const int nsteps = (nrows + RS - 1) / RS;
+
+  // ---- staging, as above: piece = (row of the stage, 4 consecutive columns)
+  const int a_q = tid % AQ, a_row = tid / AQ;
+  const bool a_colok = 4 * a_q < N;
+  int a_base[2], a_lim[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    a_base[i] = static_cast<int>(((r_begin + a_row + AROWS * i) * N + 4 * a_q) * 4);
+    a_lim[i] = a_colok ? nrows - (a_row + AROWS * i) : 0;
+  }
+  const int a_step = RS * N * 4;
+  const int x_q = tid & 7, x_row = tid >> 3;
+  const bool x_colok = c0 + 4 * x_q < Cin;
+  int x_base[XP], x_lim[XP];
+#pragma unroll
+  for (int i = 0; i < XP; ++i) {
+    const long pix = r_begin + W + 1 + x_row + 32 * i;
+    x_base[i] = static_cast<int>((pix * Cin + c0 + 4 * x_q) * 4);
+    x_lim[i] = (x_colok && R - pix > 0) ? static_cast<int>(R - pix) : 0;
+  }
+  const int x_step = RS * Cin * 4;
+  const bool do_bias = db_part != nullptr && ch == 0;
+  float bs[4] = {0.f, 0.f, 0.f, 0.f};
+  uint4 ra[2], rx[XP];
+  auto load_stage = [&](int j) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const auto v =
+          __builtin_amdgcn_raw_buffer_load_b128(yr, j * RS < a_lim[i] ? a_base[i] + j * a_step : kOOB, 0, 0);
+      ra[i] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+#pragma unroll
+    for (int i = 0; i < XP; ++i) {
+      const auto v =
+          __builtin_amdgcn_raw_buffer_load_b128(xr, j * RS < x_lim[i] ? x_base[i] + j * x_step : kOOB, 0, 0);
+      rx[i] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+  };
+  const int a_dst = a_row * SA + a_q * 8;
+  auto store_a = [&]() {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      split_store(pa, C::PA, a_dst + AROWS * i * SA, ra[i]);
+      bs[0] += __uint_as_float(ra[i].x);
+      bs[1] += __uint_as_float(ra[i].y);
+      bs[2] += __uint_as_float(ra[i].z);
+      bs[3] += __uint_as_float(ra[i].w);
+    }
+  };
+  const int x_dst0 = (2 * (W + 1) + x_row) * SX + x_q * 8;      // + j RS SX, modulo the ring
+  auto store_stage = [&](int j) {
+    store_a();
+#pragma unroll
+    for (int i = 0; i < XP; ++i) split_store(px, C::PX, (x_dst0 + (j * RS + 32 * i) * SX) & (RINGB - 1), rx[i]);
+  };
+
+  // ---- fragment addressing, as above; the wave's rows of a stage start at 16 wr
+  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+  const int rr0 = 16 * wr + 8 * (g >> 1) + tq;
+  const int a_off = rr0 * SA + (32 * wn + 16 * (g & 1) + 4 * tp) * 2;
+  const int x_col = (16 * (g & 1) + 4 * tp) * 2;
+  const int x_off0 = (W + 1 + rr0) * SX + x_col;
+  const int x_zero = RINGB + x_col;
+  int shb[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) shb[t] = ((t / 3 - 1) * W + (t % 3 - 1)) * SX;
+  int py[2], pxx[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int rem = static_cast<int>((r_begin + rr0 + 4 * r) % HW);
+    py[r] = rem / W;
+    pxx[r] = rem - py[r] * W;
+  }
+  const int adv = RS % HW, adv_y = adv / W, adv_x = adv - adv_y * W;
+
+  f16v acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+
+  // ---- prologue: the zero row, stage 0's window (RS + 2 W + 2 rows from pixel r_begin - (W + 1)) and dY rows
+  for (int i = tid; i < 3 * SX / 4; i += 256)
+    *reinterpret_cast<unsigned*>(px + (i / (SX / 4)) * C::PX + RINGB + (i % (SX / 4)) * 4) = 0u;
+  load_stage(0);
+  {
+    const int npieces = (RS + 2 * W + 2) * (CC / 4);
+    for (int piece = tid; piece < npieces; piece += 256) {
+      const int row = piece >> 3;
+      const long pix = r_begin - (W + 1) + row;
+      const bool ok = x_colok && pix >= 0 && pix < R;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(
+          xr, ok ? (static_cast<int>(pix) * Cin + c0 + 4 * x_q) * 4 : kOOB, 0, 0);
+      split_store(px, C::PX, row * SX + x_q * 8, make_uint4(v[0], v[1], v[2], v[3]));
+    }
+  }
+  store_a();
+  __syncthreads();
+
+  for (int j = 0; j < nsteps; ++j) {
+    const bool more = j + 1 < nsteps;
+    if (more) load_stage(j + 1);
+    int ok[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      ok[r] = conv_tap_mask_yx(py[r], pxx[r], H, W);
+      pxx[r] += adv_x;
+      py[r] += adv_y;
+      if (pxx[r] >= W) { pxx[r] -= W; ++py[r]; }
+      if (py[r] >= H) py[r] -= H;
+    }
+    const char* ap = pa + a_off;
+    Split3 fa;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) fa.p[p] = tr_frag(ap + p * C::PA, ap + p * C::PA + 4 * SA);
+    const int xs = x_off0 + j * RS * SX;
+    auto read_x = [&](int t) {
+      const int m0 = __builtin_amdgcn_sbfe(ok[0], t, 1), m1 = __builtin_amdgcn_sbfe(ok[1], t, 1);
+      const int o0 = (((xs + shb[t]) & (RINGB - 1)) & m0) | (x_zero & ~m0);
+      const int o1 = (((xs + 4 * SX + shb[t]) & (RINGB - 1)) & m1) | (x_zero & ~m1);
+      Split3 f;
+#pragma unroll
+      for (int p = 0; p < 3; ++p) f.p[p] = tr_frag(px + p * C::PX + o0, px + p * C::PX + o1);
+      return f;
+    };
+    Split3 fb[2];
+    fb[0] = read_x(0);
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      if (t + 1 < 9) fb[(t + 1) & 1] = read_x(t + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      acc[t] = mfma_x6(fa, fb[t & 1], acc[t]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (more) {
+      __syncthreads();                                          // every wave has read stage j: its rows may go
+      store_stage(j + 1);
+    }
+    __syncthreads();
+  }
+
+  // ---- the WR copies: wr = 1, 2, .. hand theirs to wr = 0 through the LDS (the planes are idle), TH taps a pass
+  float* const red = reinterpret_cast<float*>(smem);
+#pragma unroll
+  for (int r = 1; r < WR; ++r)
+#pragma unroll
+    for (int t0 = 0; t0 < 9; t0 += C::TH) {
+      if (wr == r) {
+#pragma unroll
+        for (int t = t0; t < t0 + C::TH && t < 9; ++t)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) red[((wn * C::TH + t - t0) * 16 + e) * 64 + lane] = acc[t][e];
+      }
+      __syncthreads();
+      if (wr == 0) {
+#pragma unroll
+        for (int t = t0; t < t0 + C::TH && t < 9; ++t)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[t][e] += red[((wn * C::TH + t - t0) * 16 + e) * 64 + lane];
+      }
+      __syncthreads();
+    }
+
+  // accumulator t register e: n = 32 wn + (e & 3) + 8 (e >> 2) + 4 h, k = t Cin + c0 + l32
+  float* outp = dw_part + static_cast<long>(s) * part_stride;
+  const int c = c0 + l32;
+  if (wr == 0 && c < Cin) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int n = 32 * wn + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (n < N) outp[static_cast<long>(n) * K + t * Cin + c] = acc[t][e];
+      }
+  }
+  if (do_bias) {
+    // red[a_row][column]: thread tid holds columns 4 a_q .. + 3 of rows a_row, a_row + AROWS of every stage
+#pragma unroll
+    for (int q = 0; q < 4; ++q) red[a_row * BN + 4 * a_q + q] = bs[q];
+    __syncthreads();
+    if (tid < N) {
+      float v = red[tid];
+      for (int i = 1; i < AROWS; ++i) v += red[i * BN + tid];
+      db_part[static_cast<long>(s) * part_stride + tid] = v;
+    }
+  }
+}
+
+template <int WN>
+void launch_wg_halo_narrow(const float* dy, const float* x, float* dwp, float* dbp, long ps, long R, int N, int K,
+                           int H, int W, int Cin, int S, long rps, hipStream_t st) {
+  const int chunks = (Cin + kWgCC - 1) / kWgCC;
+  const long nwg = static_cast<long>(S) * chunks;
+  hipLaunchKernelGGL((conv_wgrad_f32_halo_narrow_kernel<WN>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st, dy,
+                     x, dwp, dbp, ps, R, N, K, H, W, Cin, rps, chunks);
+}
+
+// APPLESTAR_CONV_WGRAD_HALO_F32 / set_conv_wgrad_halo_f32_mode: bits 1 = at most 32, 2 = 33 .. 64, 4 = 128-multiples
+// of outputs; 0 = the kernels of wgrad_f32.hip for every conv.  Default 7: every class passed its measurement
+// (docs/PERF_LOG.md)
 int& wg_halo_ref() {
   static int v = [] {
     const char* e = std::getenv("APPLESTAR_CONV_WGRAD_HALO_F32");
-    return e ? std::atoi(e) & 7 : 4;
+    return e ? std::atoi(e) & 7 : 7;
+  }();
+  return v;
+}
+
+// target workgroup count of the narrow classes' slices (APPLESTAR_CONV_WGRAD_HALO_WG): the resident slots, two
+// per CU.  The step's six narrow shapes at 256 / 512 / 1024 / 2048: 64 -> 32 at 76 x 80 563 / 480 / 490 / 532 us,
+// 32 -> 32 at 19 x 20 36 / 35 / 50 / 58 us (docs/PERF_LOG.md)
+long wg_halo_narrow_target() {
+  static const long v = [] {
+    const char* e = std::getenv("APPLESTAR_CONV_WGRAD_HALO_WG");
+    const long x = e ? std::atol(e) : 512;
+    return x >= 1 ? x : 512;
   }();
   return v;
 }
@@ -308,20 +582,39 @@ int& wg_halo_ref() {
 int conv_wgrad_halo_f32_mode() { return wg_halo_ref(); }
 void set_conv_wgrad_halo_f32_mode(int mode) { wg_halo_ref() = mode & 7; }
 
-// 32 / 64 outputs: no tile of this design fits them (a 32-wide output tile needs a 128-channel chunk to fill four
-// waves, whose window at W = 80 exceeds the LDS), so those classes stay on wgrad_f32.hip whatever the switch says
+// 128-multiples of outputs: the four waves along the outputs; at most 64 (a multiple of 4): along the reduction rows
 bool conv_wgrad_f32_halo_supported(int N, int H, int W, int Cin) {
-  return f32_mfma_mode() == 1 && H > 0 && W > 0 && W <= kWgMaxW && Cin > 0 && Cin % 16 == 0 && N > 0 && N % 128 == 0;
+  return f32_mfma_mode() == 1 && H > 0 && W > 0 && W <= kWgMaxW && Cin > 0 && Cin % 16 == 0 && N > 0 &&
+         (N % 128 == 0 || (N <= 64 && N % 4 == 0));
 }
 
 bool conv_wgrad_f32_halo_selected(int N, int H, int W, int Cin) {
-  const int bit = N == 32 ? 1 : (N == 64 ? 2 : 4);
+  const int bit = N <= 32 ? 1 : (N <= 64 ? 2 : 4);
   return (conv_wgrad_halo_f32_mode() & bit) != 0 && conv_wgrad_f32_halo_supported(N, H, W, Cin);
+}
+
+// Slices of a conv weight gradient.  The narrow classes of the halo kernel have one workgroup per slice and
+// 32-channel chunk (wgrad_f32_splits counts the per-tap kernels' (32 or 64) x 128 tiles: 5 for 64 -> 32 against 2
+// chunks here), so their count is the target over the chunks; a slice holds at least two stages and the partials
+// stay under the 64 MB of wgrad_f32_splits.  Every other conv: wgrad_f32_splits
+int conv_wgrad_f32_splits(long R, int N, int K, int H, int W, int Cin) {
+  if (!(N <= 64 && conv_wgrad_f32_halo_selected(N, H, W, Cin))) return wgrad_f32_splits(R, N, K);
+  const long chunks = (Cin + kWgCC - 1) / kWgCC, rs = N <= 32 ? WgNarrowCfg<1>::RS : WgNarrowCfg<2>::RS;
+  long S = (wg_halo_narrow_target() + chunks - 1) / chunks;
+  const long max_s = (R + 2 * rs - 1) / (2 * rs);
+  if (S > max_s) S = max_s;
+  const long max_part = (16L << 20) / (static_cast<long>(N) * K);
+  if (S > max_part) S = max_part;
+  if (S < 1) S = 1;
+  return static_cast<int>(S);
 }
 
 void conv_wgrad_f32_halo(const float* dy, const float* x, float* dw_part, float* db_part, long part_stride, long R,
                          int N, int K, int H, int W, int Cin, int S, long rows_per_split, hipStream_t st) {
-  if (W <= 40) launch_wg_halo<40>(dy, x, dw_part, db_part, part_stride, R, N, K, H, W, Cin, S, rows_per_split, st);
+  if (N <= 32) launch_wg_halo_narrow<1>(dy, x, dw_part, db_part, part_stride, R, N, K, H, W, Cin, S, rows_per_split, st);
+  else if (N <= 64)
+    launch_wg_halo_narrow<2>(dy, x, dw_part, db_part, part_stride, R, N, K, H, W, Cin, S, rows_per_split, st);
+  else if (W <= 40) launch_wg_halo<40>(dy, x, dw_part, db_part, part_stride, R, N, K, H, W, Cin, S, rows_per_split, st);
   else launch_wg_halo<kWgMaxW>(dy, x, dw_part, db_part, part_stride, R, N, K, H, W, Cin, S, rows_per_split, st);
 }
 

@@ -764,7 +764,8 @@ void wgrad_f32(const float* dy, const float* x, float* dw_part, float* db_part, 
   long rps = (R + S - 1) / S;
   rps = (rps + 31) / 32 * 32;
   const bool conv = Cin > 0;
-  // halo-window conv gradient (conv_wgrad_f32_halo.hip): same slices and partials, all nine taps per workgroup
+  // halo-window conv gradient (conv_wgrad_f32_halo.hip): same partials, all nine taps per workgroup; S is
+  // conv_wgrad_f32_splits' (its own count for at most 64 outputs, wgrad_f32_splits' otherwise)
   if (conv && conv_wgrad_f32_halo_selected(N, H, W, Cin)) {
     conv_wgrad_f32_halo(dy, x, dw_part, db_part, part_stride, R, N, K, H, W, Cin, S, rps, st);
     return;

@@ -6,8 +6,9 @@
 Per shape: ``pairs`` times (parent, halo), each the median of ``iters`` HIP-event timings of one call (slices +
 column reduction, as the learner runs it); one JSON line per measurement and a verdict line per shape: the halo
 kernel wins if in every pair its median is below the parent's by more than the spread of the parent's medians.
-The default shapes are the learner step's conv weight gradients with 128-multiples of outputs (the class the halo
-kernel takes) at B = 390 (spatial encoder) and 384 (location head); others run the parent under either switch.
+The default shapes are the learner step's conv weight gradients at B = 390 (spatial encoder) and 384 (location
+head): 128 outputs, then the narrow classes (16, 32 and 64 outputs); a shape the halo kernel declines runs the
+parent under either switch.
 """
 import argparse
 import json
@@ -19,7 +20,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-SHAPES = [(390, 19, 20, 128, 128), (384, 19, 20, 128, 128), (390, 38, 40, 64, 128)]
+SHAPES = [(390, 19, 20, 128, 128), (384, 19, 20, 128, 128), (390, 38, 40, 64, 128),
+          # at most 64 outputs (switch bits 1 and 2: the waves along the reduction rows)
+          (384, 76, 80, 64, 32), (390, 76, 80, 32, 64), (384, 38, 40, 128, 64), (390, 19, 20, 32, 32),
+          (390, 76, 80, 16, 16), (390, 38, 40, 16, 32)]
 
 
 def median_us(fn, iters):
