@@ -2238,6 +2238,140 @@ std::vector<at::Tensor> rl_loss(const at::Tensor& alp, const at::Tensor& blp, co
   return {info, dalp, dent, dkl, dv};
 }
 
+// ---------------------------------------------------------------- fused supervised loss (sl_loss.hip)
+namespace {
+const uint8_t* mask_ptr(const at::Tensor& t, int64_t n, const char* what) {
+  check_cuda(t, what);
+  TORCH_CHECK((t.scalar_type() == at::kBool || t.scalar_type() == at::kByte) && t.is_contiguous() && t.numel() == n,
+              "sl_loss: ", what, " bool / uint8 contiguous of ", n, " elements");
+  return static_cast<const uint8_t*>(t.data_ptr());
+}
+
+struct SLCeArgs {
+  const uint8_t* row_on = nullptr;
+  const int64_t* su_len = nullptr;
+  const uint8_t* su_on = nullptr;
+  int S = 1;
+};
+
+// the checks shared by the forward and the backward of the per-row cross entropy
+SLCeArgs sl_ce_check(const at::Tensor& logits, const at::Tensor& labels, const c10::optional<at::Tensor>& row_on,
+                     const c10::optional<at::Tensor>& su_len, const c10::optional<at::Tensor>& su_on, int64_t S) {
+  check_cuda(logits, "logits");
+  check_cuda(labels, "labels");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "sl_ce: logits [R, C] contiguous");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16, "sl_ce: logits dtype");
+  const int64_t R = logits.size(0), C = logits.size(1);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous() && labels.numel() == R,
+              "sl_ce: labels int64 [R]");
+  TORCH_CHECK(C > 0 && C < (1 << 30), "sl_ce: C");
+  SLCeArgs a;
+  TORCH_CHECK(su_len.has_value() == su_on.has_value(), "sl_ce: su_len and su_on go together");
+  if (su_len.has_value()) {
+    TORCH_CHECK(!row_on.has_value(), "sl_ce: row_on and the selected-units form exclude each other");
+    TORCH_CHECK(S >= 1 && S <= 64 && R % S == 0 && C <= as::sl_ce_su_max_c(), "sl_ce: selected units S <= 64, C <= ",
+                as::sl_ce_su_max_c());
+    const int64_t b = R / S;
+    check_cuda(*su_len, "su_len");
+    TORCH_CHECK(su_len->scalar_type() == at::kLong && su_len->is_contiguous() && su_len->numel() == b,
+                "sl_ce: su_len int64 [b]");
+    a.su_len = su_len->data_ptr<int64_t>();
+    a.su_on = mask_ptr(*su_on, b, "su_on");
+    a.S = static_cast<int>(S);
+  } else if (row_on.has_value()) {
+    a.row_on = mask_ptr(*row_on, R, "row_on");
+  }
+  return a;
+}
+}  // namespace
+
+// logits [R, C] fp32/bf16, labels [R] int64 -> {loss [R] fp32, argmax [R] int64, stats [R, 2] fp32}
+std::vector<at::Tensor> sl_ce_fwd(const at::Tensor& logits, const at::Tensor& labels, double eps,
+                                  const c10::optional<at::Tensor>& row_on, const c10::optional<at::Tensor>& su_len,
+                                  const c10::optional<at::Tensor>& su_on, int64_t S, bool su_mask) {
+  const SLCeArgs a = sl_ce_check(logits, labels, row_on, su_len, su_on, S);
+  TORCH_CHECK(eps >= 0.0 && eps < 1.0, "sl_ce: eps");
+  const int64_t R = logits.size(0), C = logits.size(1);
+  c10::hip::HIPGuard g(logits.device().index());
+  auto loss = at::empty({R}, logits.options().dtype(at::kFloat));
+  auto amax = at::empty({R}, logits.options().dtype(at::kLong));
+  auto stats = at::empty({R, 2}, logits.options().dtype(at::kFloat));
+  as::sl_ce_fwd(logits.data_ptr(), dt(logits), labels.data_ptr<int64_t>(), a.row_on, a.su_len, a.su_on, a.S,
+                su_mask ? 1 : 0, static_cast<float>(eps), loss.data_ptr<float>(), amax.data_ptr<int64_t>(),
+                stats.data_ptr<float>(), R, static_cast<int>(C), stream());
+  return {loss, amax, stats};
+}
+
+at::Tensor sl_ce_bwd(const at::Tensor& logits, const at::Tensor& labels, double eps,
+                     const c10::optional<at::Tensor>& row_on, const c10::optional<at::Tensor>& su_len,
+                     const c10::optional<at::Tensor>& su_on, int64_t S, bool su_mask, const at::Tensor& stats,
+                     const at::Tensor& grad) {
+  const SLCeArgs a = sl_ce_check(logits, labels, row_on, su_len, su_on, S);
+  const int64_t R = logits.size(0), C = logits.size(1);
+  check_cuda(grad, "grad");
+  check_cuda(stats, "stats");
+  TORCH_CHECK(grad.scalar_type() == at::kFloat && grad.is_contiguous() && grad.numel() == R, "sl_ce_bwd: grad fp32 [R]");
+  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.is_contiguous() && stats.numel() == 2 * R,
+              "sl_ce_bwd: stats");
+  c10::hip::HIPGuard g(logits.device().index());
+  auto dl = at::empty_like(logits);
+  as::sl_ce_bwd(logits.data_ptr(), dt(logits), labels.data_ptr<int64_t>(), a.row_on, a.su_len, a.su_on, a.S,
+                su_mask ? 1 : 0, static_cast<float>(eps), stats.data_ptr<float>(), grad.data_ptr<float>(),
+                dl.data_ptr(), R, static_cast<int>(C), stream());
+  return dl;
+}
+
+// five flat heads (action_type, delay, queued, target_unit, target_location): losses fp32 [b], argmaxes / labels
+// int64 [b], masks bool [b]; su_loss fp32 [b, S], su_labels int64 [b, S], su_len int64 [b], su_on bool [b];
+// preds int64 [b, S] with ent_num int64 [b] (both or neither); w fp32 [6]; cr_scale fp32 [1]; n: unit-id range
+// -> {info [15], g_flat [5, b], g_su [b, S]}
+std::vector<at::Tensor> sl_loss_tail(const std::vector<at::Tensor>& losses, const std::vector<at::Tensor>& argmaxes,
+                                     const std::vector<at::Tensor>& labels, const std::vector<at::Tensor>& masks,
+                                     const at::Tensor& su_loss, const at::Tensor& su_labels, const at::Tensor& su_len,
+                                     const at::Tensor& su_on, const c10::optional<at::Tensor>& preds,
+                                     const c10::optional<at::Tensor>& ent_num, const at::Tensor& w,
+                                     const at::Tensor& cr_scale, int64_t n) {
+  TORCH_CHECK(losses.size() == 5 && argmaxes.size() == 5 && labels.size() == 5 && masks.size() == 5,
+              "sl_loss_tail: five flat heads");
+  check_cuda(su_loss, "su_loss");
+  TORCH_CHECK(su_loss.dim() == 2 && su_loss.scalar_type() == at::kFloat && su_loss.is_contiguous(),
+              "sl_loss_tail: su_loss fp32 [b, S] contiguous");
+  const int64_t b = su_loss.size(0), S = su_loss.size(1);
+  TORCH_CHECK(b >= 1 && b <= 2048 && S >= 1 && S <= 64 && n >= 1 && n <= as::sl_ce_su_max_c(),
+              "sl_loss_tail: b <= 2048, S <= 64, n <= ", as::sl_ce_su_max_c());
+  auto i64 = [&](const at::Tensor& t, int64_t numel, const char* what) {
+    check_cuda(t, what);
+    TORCH_CHECK(t.scalar_type() == at::kLong && t.is_contiguous() && t.numel() == numel, "sl_loss_tail: ", what,
+                " int64 contiguous of ", numel, " elements");
+    return t.data_ptr<int64_t>();
+  };
+  auto f32 = [&](const at::Tensor& t, int64_t numel, const char* what) {
+    check_cuda(t, what);
+    TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == numel, "sl_loss_tail: ", what,
+                " fp32 contiguous of ", numel, " elements");
+    return t.data_ptr<float>();
+  };
+  as::SLTailHeads H;
+  for (int f = 0; f < 5; ++f) {
+    H.loss[f] = f32(losses[f], b, "loss");
+    H.amax[f] = i64(argmaxes[f], b, "argmax");
+    H.lab[f] = i64(labels[f], b, "labels");
+    H.mask[f] = mask_ptr(masks[f], b, "mask");
+  }
+  TORCH_CHECK(preds.has_value() == ent_num.has_value(), "sl_loss_tail: preds and ent_num go together");
+  const int64_t* pp = preds.has_value() ? i64(*preds, b * S, "preds") : nullptr;
+  const int64_t* ep = ent_num.has_value() ? i64(*ent_num, b, "ent_num") : nullptr;
+  c10::hip::HIPGuard g(su_loss.device().index());
+  auto info = at::empty({15}, su_loss.options());
+  auto g_flat = at::empty({5, b}, su_loss.options());
+  auto g_su = at::empty({b, S}, su_loss.options());
+  as::sl_loss_tail(H, su_loss.data_ptr<float>(), i64(su_labels, b * S, "su_labels"), i64(su_len, b, "su_len"),
+                   mask_ptr(su_on, b, "su_on"), pp, ep, f32(w, 6, "w"), f32(cr_scale, 1, "cr_scale"),
+                   static_cast<int>(b), static_cast<int>(S), static_cast<int>(n), info.data_ptr<float>(),
+                   g_flat.data_ptr<float>(), g_su.data_ptr<float>(), stream());
+  return {info, g_flat, g_su};
+}
+
 // ---------------------------------------------------------------- ordered gather / scatter (ordered.hip)
 // key [B, N1, C] fp32 / bf16, labels [B, S] int64 -> key rows [B, S, C] (labels clamped to [0, N1))
 at::Tensor gather_steps_fwd(const at::Tensor& key, const at::Tensor& labels) {
@@ -2635,6 +2769,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rl_loss", &rl_loss, py::arg("alp"), py::arg("blp"), py::arg("hm"), py::arg("ent"), py::arg("kl"), py::arg("v"),
         py::arg("r"), py::arg("wm"), py::arg("atflag"), py::arg("sc"), py::arg("upgo_f"), py::arg("only_value"),
         py::arg("ordered") = false, py::arg("sk") = py::none(), py::arg("dflag") = py::none());
+  m.def("sl_ce_fwd", &sl_ce_fwd, py::arg("logits"), py::arg("labels"), py::arg("eps"), py::arg("row_on") = py::none(),
+        py::arg("su_len") = py::none(), py::arg("su_on") = py::none(), py::arg("S") = 1, py::arg("su_mask") = false);
+  m.def("sl_ce_bwd", &sl_ce_bwd, py::arg("logits"), py::arg("labels"), py::arg("eps"), py::arg("row_on"),
+        py::arg("su_len"), py::arg("su_on"), py::arg("S"), py::arg("su_mask"), py::arg("stats"), py::arg("grad"));
+  m.def("sl_loss_tail", &sl_loss_tail, py::arg("losses"), py::arg("argmaxes"), py::arg("labels"), py::arg("masks"),
+        py::arg("su_loss"), py::arg("su_labels"), py::arg("su_len"), py::arg("su_on"), py::arg("preds"),
+        py::arg("ent_num"), py::arg("w"), py::arg("cr_scale"), py::arg("n"));
+  m.def("sl_ce_su_max_c", []() { return as::sl_ce_su_max_c(); });
   m.def("gate_chain", &gate_chain);
   m.def("gate_chain_f32", &gate_chain_f32);
   m.def("vsp_pool_fwd", &vsp_pool_fwd);

@@ -554,6 +554,33 @@ void rl_loss_dapo(const float* alp, const float* blp, const float* hm, const flo
                   const float* dflag, const float* sc, int F, int T, int B, int upgo_f, int only_value, bool ordered,
                   float* dalp, float* dent, float* dkl, float* dsk, float* dv, float* info, hipStream_t s);
 
+// ---- sl_loss.hip: fused supervised loss (per-row cross entropy + one-workgroup tail) ----------------
+// per row of logits l [R, C] and label lab [R]: loss [R] (cross entropy, label smoothing eps), argmax [R] (lowest
+// index of the maximum), stats [R, 2] = (max, log sum exp shifted).  row_on [R] (may be null): rows at 0 are not read
+// (loss 0, argmax -1).  Selected-units form when su_len != null: R = b * S, lab [b, S], su_len [b], su_on [b]; rows
+// past su_len or of su_on == 0 are off; su_mask: the other labelled units of the observation read as -1e9.
+// C <= sl_ce_su_max_c() and S <= 64 in that form.
+int sl_ce_su_max_c();
+void sl_ce_fwd(const void* l, int l_dt, const long* lab, const uint8_t* row_on, const long* su_len,
+               const uint8_t* su_on, int S, int su_mask, float eps, float* loss, long* amax, float* stats, long R, int C,
+               hipStream_t s);
+// dl [R, C] (l's dtype) = g_r (softmax - (1 - eps) onehot - eps / C); zero at masked columns, off rows and g_r == 0
+void sl_ce_bwd(const void* l, int l_dt, const long* lab, const uint8_t* row_on, const long* su_len,
+               const uint8_t* su_on, int S, int su_mask, float eps, const float* stats, const float* g, void* dl, long R,
+               int C, hipStream_t s);
+struct SLTailHeads {                     // the five flat heads (action_type, delay, queued, target_unit, target_location)
+  const float* loss[5];                  // [b] row losses
+  const long* amax[5];                   // [b] argmax
+  const long* lab[5];                    // [b] labels
+  const uint8_t* mask[5];                // [b] head mask (0 / non-zero)
+};
+// info [15] (layout in sl_loss.hip, total last), g_flat [5, b] and g_su [b, S]: d total / d row loss.
+// w [6] loss weights in HEADS order; cr_scale [1]: 0 = masked means, else world / total batch; preds (may be null)
+// [b, S] predicted units with ent_num [b] for the IoU over unit ids < n.  S <= 64, n <= sl_ce_su_max_c().
+void sl_loss_tail(const SLTailHeads& heads, const float* su_loss, const long* su_lab, const long* su_len,
+                  const uint8_t* su_on, const long* preds, const long* ent_num, const float* w, const float* cr_scale,
+                  int b, int S, int n, float* info, float* g_flat, float* g_su, hipStream_t s);
+
 // ---- ordered.hip: order-fixed sums of the deterministic mode (no float atomics; idt codes as embed_relu_fwd)
 // workgroups of table_grad_ordered for U rows (single: one workgroup, the result written outright)
 int table_grad_ordered_blocks(long U, bool single);

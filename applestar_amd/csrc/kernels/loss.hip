@@ -29,37 +29,10 @@
 
 #include "../common.h"
 #include "../kernels.h"
+#include "../row_reduce.h"
 
 namespace as {
 namespace {
-
-template <int TPR>
-__device__ __forceinline__ float group_max(float v, float* red) {
-  v = wave_max(v);
-  if constexpr (TPR == 64) {
-    return v;
-  } else {
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  }
-}
-
-template <int TPR>
-__device__ __forceinline__ float group_sum(float v, float* red) {
-  v = wave_sum(v);
-  if constexpr (TPR == 64) {
-    return v;
-  } else {
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-  }
-}
 
 // stats [R, 6]: m, log s, H, mt, log st, (unused); SUCC: out [4, R], stats [R, 8]: ..., mu, log su, (unused)
 template <typename LT, typename TT, int TPR, bool SUCC>

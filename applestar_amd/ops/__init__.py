@@ -215,6 +215,28 @@ def head_stats(logits, teacher, actions, successive=None):
     return ref.head_stats(logits, teacher, actions, successive)
 
 
+def sl_head_ce(logits, labels, eps: float = 0.0, row_on=None, su=None, su_mask: bool = False):
+    """(cross entropy with label smoothing ``eps``, argmax) per row of ``logits [..., C]``, shaped like ``labels``
+    (``reference.sl_head_ce``; sl_loss.hip on the GPU).  ``row_on``: rows at 0 are not read (loss 0, argmax -1);
+    ``su = (su_len, su_on)``: the selected-units form over logits [b, S, C], with ``su_mask`` the other labelled units
+    of the observation read as -1e9."""
+    n = _native(logits)
+    if n is not None and n.has('sl_loss'):
+        return n.sl_head_ce(logits, labels, eps, row_on, su, su_mask)
+    return ref.sl_head_ce(logits, labels, eps, row_on, su, su_mask)
+
+
+def sl_loss_tail(losses, argmaxes, labels, masks, su_loss, su_labels, su_len, su_on, preds, ent_num, w, cr_scale, n):
+    """(total, info [15] in ``reference.SL_INFO_KEYS`` order) of the supervised loss after the per-row cross
+    entropies (``reference.sl_loss_tail``; one native workgroup on the GPU, where only the total carries gradient)."""
+    nat = _native(su_loss)
+    if nat is not None and nat.has('sl_loss'):
+        return nat.sl_loss_tail(losses, argmaxes, labels, masks, su_loss, su_labels, su_len, su_on, preds, ent_num, w,
+                                cr_scale, n)
+    return ref.sl_loss_tail(losses, argmaxes, labels, masks, su_loss, su_labels, su_len, su_on, preds, ent_num, w,
+                            cr_scale, n)
+
+
 def scatter_connection(proj, x, y, H: int, W: int):
     """Sum the unit rows proj [B, N, C] into a [B, C, H, W] map.  GPU in deterministic mode: the native kernel that
     adds each pixel's rows in ascending unit index; otherwise the torch index_add_ (atomics on the GPU)."""

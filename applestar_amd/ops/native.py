@@ -28,7 +28,7 @@ _IMPLEMENTED = {'entity_mean_pool', 'layer_norm', 'gated_residual', 'reverse_sca
                 'spatial_embed', 'varlen_attention', 'su_sample', 'upsample_conv_out', 'maxpool2x2', 'segment_sum',
                 'gather_rows', 'conv2d', 'linear', 'resblock', 'gated_resblock', 'head_stats', 'bo_encoder', 'resmlp',
                 'location_input', 'value_spatial_proj', 'spatial_embed_pool', 'value_spatial_proj_pool',
-                'rl_loss', 'embed_relu', 'col_assemble', 'entity_pack', 'action_logp'}
+                'rl_loss', 'embed_relu', 'col_assemble', 'entity_pack', 'action_logp', 'sl_loss'}
 
 
 # Deterministic mode (docs/OPEN_ISSUES.md "Determinism"): the sites that sum with float atomics, or through torch's
@@ -2545,6 +2545,88 @@ def head_stats(logits, teacher, actions, successive=None):
         return logp_a.view(lead), ent.view(lead), kl.view(lead), klu.view(lead)
     logp_a, ent, kl = _HeadStats.apply(l2, t2, a)
     return logp_a.view(lead), ent.view(lead), kl.view(lead)
+
+
+# ---------------------------------------------------------------------------- fused supervised loss
+SL_LOSS_MAX_B, SL_LOSS_MAX_S, SL_LOSS_MAX_N = 2048, 64, 1024   # limits of the tail / the selected-units form
+
+
+def _mask_u8(m):
+    """A 0 / non-zero mask as the contiguous bool / uint8 tensor the kernels read (a bool mask is passed as is)."""
+    m = m.detach()
+    if m.dtype not in (torch.bool, torch.uint8):
+        m = m != 0
+    return m.contiguous()
+
+
+class _SLHeadCE(torch.autograd.Function):
+    """(cross entropy, argmax) per row in one kernel; backward one pass over the row (sl_loss.hip)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, eps, row_on, su_len, su_on, S, su_mask):
+        loss, amax, stats = _C.sl_ce_fwd(logits, labels, eps, row_on, su_len, su_on, S, su_mask)
+        ctx.save_for_backward(logits, labels, row_on, su_len, su_on, stats)
+        ctx.args = (eps, S, su_mask)
+        ctx.mark_non_differentiable(amax)
+        ctx.set_materialize_grads(False)
+        return loss, amax
+
+    @staticmethod
+    def backward(ctx, g, _gamax):
+        logits, labels, row_on, su_len, su_on, stats = ctx.saved_tensors
+        eps, S, su_mask = ctx.args
+        if g is None:
+            return (None,) * 8
+        dl = _C.sl_ce_bwd(logits, labels, eps, row_on, su_len, su_on, S, su_mask, stats, g.float().contiguous())
+        return (dl,) + (None,) * 7
+
+
+def sl_head_ce(logits, labels, eps=0.0, row_on=None, su=None, su_mask=False):
+    """Fused ``reference.sl_head_ce`` for fp32 / bf16 logits [..., C]: (loss, argmax) shaped like ``labels``.  The
+    gradient has the logits' dtype.  Selected-units form: S <= 64 steps and C <= 1024 columns."""
+    C = logits.shape[-1]
+    lead = labels.shape
+    l2 = logits if logits.dtype in (torch.float32, torch.bfloat16) else logits.float()
+    l2 = l2.reshape(-1, C).contiguous()
+    lab = labels.reshape(-1).long().contiguous()
+    if su is not None:
+        su_len, su_on = su
+        loss, amax = _SLHeadCE.apply(l2, lab, float(eps), None, su_len.detach().long().contiguous(), _mask_u8(su_on),
+                                     int(lead[-1]), bool(su_mask))
+    else:
+        loss, amax = _SLHeadCE.apply(l2, lab, float(eps), None if row_on is None else _mask_u8(row_on).reshape(-1),
+                                     None, None, 1, False)
+    return loss.view(lead), amax.view(lead)
+
+
+class _SLLossTail(torch.autograd.Function):
+    """The supervised loss after the per-row cross entropies (sl_loss.hip, one workgroup): the total, the info
+    vector and the closed-form gradients w.r.t. the row losses; backward only scales them by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, su_loss, argmaxes, labels, masks, su_labels, su_len, su_on, preds, ent_num, w, cr_scale, n,
+                *losses):
+        info, g_flat, g_su = _C.sl_loss_tail([x.detach() for x in losses], argmaxes, labels, masks, su_loss.detach(),
+                                             su_labels, su_len, su_on, preds, ent_num, w, cr_scale, n)
+        ctx.save_for_backward(g_flat, g_su)
+        ctx.mark_non_differentiable(info)
+        return info[-1], info
+
+    @staticmethod
+    def backward(ctx, gtotal, _ginfo):
+        g_flat, g_su = ctx.saved_tensors
+        gf = g_flat * gtotal
+        return (g_su * gtotal,) + (None,) * 11 + tuple(gf[i] for i in range(5))
+
+
+def sl_loss_tail(losses, argmaxes, labels, masks, su_loss, su_labels, su_len, su_on, preds, ent_num, w, cr_scale, n):
+    """Fused ``reference.sl_loss_tail``: (total loss 0-d, info [15]); only the total carries gradient."""
+    i64 = lambda t: t.detach().long().contiguous()  # noqa: E731
+    f32 = lambda t: t.float().contiguous()  # noqa: E731
+    return _SLLossTail.apply(f32(su_loss), [i64(t) for t in argmaxes], [i64(t) for t in labels],
+                             [_mask_u8(m) for m in masks], i64(su_labels), i64(su_len), _mask_u8(su_on),
+                             None if preds is None else i64(preds), None if preds is None else i64(ent_num),
+                             f32(w.detach()), f32(cr_scale.detach()).reshape(1), int(n), *[f32(x) for x in losses])
 
 
 # ---------------------------------------------------------------------------- fused build-order transformer

@@ -189,6 +189,112 @@ def head_stats(logits: torch.Tensor, teacher: Optional[torch.Tensor], actions: t
     return logp_a, ent, kl, (ulp.exp() * (ulp - lp)).sum(-1)
 
 
+SL_INFO_KEYS = ('action_type_loss', 'delay_loss', 'queued_loss', 'selected_units_loss', 'target_unit_loss',
+                'target_location_loss', 'selected_units_loss_norm', 'selected_units_end_flag_loss', 'action_type_acc',
+                'delay_distance_L1', 'queued_acc', 'selected_units_iou', 'target_unit_acc',
+                'target_location_distance_L2', 'total_loss')
+SL_FLAT_HEADS = ('action_type', 'delay', 'queued', 'target_unit', 'target_location')
+
+
+def sl_head_ce(logits: torch.Tensor, labels: torch.Tensor, eps: float = 0.0, row_on: Optional[torch.Tensor] = None,
+               su=None, su_mask: bool = False):
+    """Per row of ``logits [..., C]``: (cross entropy with label smoothing ``eps``, argmax = lowest index of the
+    maximum), shaped like ``labels``; fp32 (float64 logits stay float64).  Labels are clamped to [0, C).
+    Rows where ``row_on`` is 0 are switched off: their logits are not used (loss 0, argmax -1, zero gradient).
+    Selected-units form, ``su = (su_len [b], su_on [b])`` with logits [b, S, C] and labels [b, S]: row (bi, si) is
+    off when si >= su_len[bi] or su_on[bi] == 0; with ``su_mask`` every other labelled unit of the observation
+    (labels[bi, j], j < su_len[bi] - 1, except the row's own label) reads as -1e9 (sl/loss.py _selected_units)."""
+    C = logits.shape[-1]
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    lab = labels.long()
+    on = None
+    if su is not None:
+        su_len, su_on = su
+        b, S = lab.shape
+        su_len = su_len.long()
+        on = sequence_mask(su_len, S) & (su_on != 0).unsqueeze(1)
+        if su_mask:
+            no_end = sequence_mask((su_len - 1).clamp(min=0), S) & (lab >= 0) & (lab < C)
+            other = torch.where(no_end, lab, torch.full_like(lab, C))
+            inset = torch.zeros(b, C + 1, dtype=torch.bool, device=x.device).scatter_(1, other, True)
+            forbid = inset.unsqueeze(1).expand(b, S, C + 1).clone()
+            forbid.scatter_(2, other.unsqueeze(2), False)
+            x = x.masked_fill(forbid[:, :, :C], -1e9)
+    elif row_on is not None:
+        on = row_on != 0
+    if on is not None:
+        x = torch.where(on.unsqueeze(-1), x, torch.zeros_like(x))
+    lp = torch.log_softmax(x, dim=-1)
+    loss = -lp.gather(-1, lab.clamp(0, C - 1).unsqueeze(-1)).squeeze(-1)
+    if eps > 0:
+        loss = (1 - eps) * loss + eps * (-lp.mean(-1))
+    amax = x.argmax(-1)
+    if on is not None:
+        loss = torch.where(on, loss, torch.zeros_like(loss))
+        amax = torch.where(on, amax, torch.full_like(amax, -1))
+    return loss, amax
+
+
+def sl_loss_tail(losses, argmaxes, labels, masks, su_loss, su_labels, su_len, su_on, preds, ent_num, w, cr_scale,
+                 n: int):
+    """Everything of the supervised loss after the per-row cross entropies (sl/loss.py): (total, info [15] in
+    ``SL_INFO_KEYS`` order).  ``losses / argmaxes / labels / masks``: the five flat heads (``SL_FLAT_HEADS``), [b] each;
+    ``su_loss / su_labels`` [b, S], ``su_len / su_on`` [b]; ``preds`` [b, S] with ``ent_num`` [b] or both None (IoU 0);
+    ``w`` [6] loss weights in HEADS order; ``cr_scale`` [1]: 0 = masked means, else world / total batch (every head's
+    loss is then sum(loss * mask) * cr_scale); ``n``: unit ids 0 .. n-1 enter the IoU."""
+    dt = su_loss.dtype
+    dev = su_loss.device
+    b, S = su_loss.shape
+    cr = torch.as_tensor(cr_scale, device=dev).reshape(-1)[0].to(dt)
+    cross = cr > 0
+    w = torch.as_tensor(w, device=dev).to(dt)
+    info = [None] * 15
+    loss_slot, metric_slot = (0, 1, 2, 4, 5), (8, 9, 10, 12, 13)
+    total = torch.zeros((), dtype=dt, device=dev)
+    for f in range(5):
+        m = (masks[f] != 0).to(dt)
+        sm = m.sum()
+        scale = torch.where(cross, cr, 1.0 / sm.clamp(min=1.0))
+        lh = (torch.where(m > 0, losses[f].to(dt), torch.zeros_like(m))).sum() * scale
+        p, a = argmaxes[f].long(), labels[f].long()
+        if f == 0:
+            met = (p == a).to(dt).mean()
+        elif f == 3:
+            met = ((p == a).to(dt) * m).sum() / (sm + 1e-6)
+        elif f == 4:
+            d = torch.stack([p % 160 - a % 160, p // 160 - a // 160], -1).to(dt)
+            met = (d.pow(2).sum(-1).sqrt() * m).sum() / (sm + 1e-6)
+        else:
+            met = ((p - a).abs().to(dt) * m).sum() / (sm + 1e-6)
+        info[loss_slot[f]], info[metric_slot[f]] = lh, met.detach()
+        total = total + w[loss_slot[f]] * lh
+    su_len = su_len.long()
+    on = sequence_mask(su_len, S) & (su_on != 0).unsqueeze(1)
+    sl = torch.where(on, su_loss, torch.zeros_like(su_loss))
+    lsu = sl.sum() * torch.where(cross, cr, torch.ones((), dtype=dt, device=dev) / b)
+    info[3] = lsu
+    info[6] = (sl.sum() / (su_len.sum().to(dt) + 1e-6)).detach()
+    info[7] = sl[torch.arange(b, device=dev), (su_len - 1).clamp(0, S - 1)].mean().detach()
+    total = total + w[3] * lsu
+    if preds is not None:
+        pr = preds.long()
+        is_end = pr == ent_num.long().unsqueeze(1)
+        first_end = torch.where(is_end.any(1), is_end.to(dt).argmax(1) + 1, torch.full_like(su_len, S))
+        pm = sequence_mask(first_end, S)
+        P = torch.zeros(b, n + 1, dtype=torch.bool, device=dev)
+        L = torch.zeros_like(P)
+        P.scatter_(1, ((pr + 1) * pm).clamp(0, n), True)
+        L.scatter_(1, ((su_labels.long() + 1) * sequence_mask(su_len, S)).clamp(0, n), True)
+        inter = (P & L)[:, 1:].sum(1).to(dt)
+        union = (P | L)[:, 1:].sum(1).to(dt)
+        mo = (su_on != 0).to(dt)
+        info[11] = (inter / (union + 1e-6) * mo).sum() / (mo.sum() + 1e-6)
+    else:
+        info[11] = torch.zeros((), dtype=dt, device=dev)
+    info[14] = total
+    return total, torch.stack([v.detach() for v in info])
+
+
 def vtrace_advantages(clipped_rhos, clipped_cs, rewards, values, gamma: float = 1.0, lambda_: float = 1.0):
     """as_rl_utils.py:284-312. rhos/cs/rewards [T,B], values [T+1,B] -> advantages [T,B]."""
     T = rewards.shape[0]
