@@ -618,7 +618,15 @@ at::Tensor varlen_attn_bwd(const at::Tensor& qkv, const at::Tensor& out, const a
 }
 
 
+std::vector<at::Tensor> varlen_attn_fwd_f32_planes(const at::Tensor& planes, const at::Tensor& cu, int64_t max_len,
+                                                   int64_t H);
+at::Tensor varlen_attn_bwd_f32_planes(const at::Tensor& planes, const at::Tensor& out, const at::Tensor& dout,
+                                      const at::Tensor& lse, const at::Tensor& cu, int64_t max_len, int64_t H);
+
+// qkv: fp32 [T, 3*H*128], or its three bf16 parts [3, T, 3*H*128] as gemm_f32_psb_planes writes them (the plane
+// kernels: the same products, the same out / lse)
 std::vector<at::Tensor> varlen_attn_fwd_f32(const at::Tensor& qkv, const at::Tensor& cu, int64_t max_len, int64_t H) {
+  if (qkv.scalar_type() == at::kBFloat16) return varlen_attn_fwd_f32_planes(qkv, cu, max_len, H);
   check_cuda(qkv, "qkv");
   check_cuda(cu, "cu_seqlens");
   TORCH_CHECK(qkv.scalar_type() == at::kFloat && qkv.dim() == 2 && qkv.size(1) == 3 * H * 128 && qkv.is_contiguous(),
@@ -636,6 +644,7 @@ std::vector<at::Tensor> varlen_attn_fwd_f32(const at::Tensor& qkv, const at::Ten
 
 at::Tensor varlen_attn_bwd_f32(const at::Tensor& qkv, const at::Tensor& out, const at::Tensor& dout,
                                const at::Tensor& lse, const at::Tensor& cu, int64_t max_len, int64_t H) {
+  if (qkv.scalar_type() == at::kBFloat16) return varlen_attn_bwd_f32_planes(qkv, out, dout, lse, cu, max_len, H);
   check_cuda(dout, "dout");
   TORCH_CHECK(qkv.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat && dout.scalar_type() == at::kFloat &&
               dout.sizes() == out.sizes() && dout.is_contiguous() && out.is_contiguous(), "varlen_attn_bwd_f32: fp32");
@@ -647,6 +656,58 @@ at::Tensor varlen_attn_bwd_f32(const at::Tensor& qkv, const at::Tensor& out, con
     as::varlen_attn_bwd_f32(qkv.data_ptr<float>(), out.data_ptr<float>(), dout.data_ptr<float>(), lse.data_ptr<float>(),
                             cu.data_ptr<int>(), dqkv.data_ptr<float>(), delta.data_ptr<float>(), S, max_len, H, T,
                             1.0f / std::sqrt(128.0f), stream());
+  return dqkv;
+}
+
+bool varlen_attn_planes_supported(int64_t H, int64_t T) {
+  return as::f32_mfma_mode() != 0 && as::varlen_attn_planes_supported(static_cast<int>(H), T);
+}
+
+static void check_qkv_planes(const at::Tensor& planes, int64_t H) {
+  check_cuda(planes, "qkv planes");
+  TORCH_CHECK(planes.scalar_type() == at::kBFloat16 && planes.dim() == 3 && planes.size(0) == 3 &&
+                  planes.size(2) == 3 * H * 128 && planes.is_contiguous(),
+              "varlen_attn_f32_planes: qkv planes bf16 contiguous [3, T, 3*H*128]");
+  TORCH_CHECK(varlen_attn_planes_supported(H, planes.size(1)) || planes.size(1) == 0,
+              "varlen_attn_f32_planes: needs split-MFMA mode and planes below 2^31 bytes");
+}
+
+// fp32 attention on qkv given as the bf16 planes of gemm_f32_psb_planes: out / lse equal varlen_attn_fwd_f32's
+std::vector<at::Tensor> varlen_attn_fwd_f32_planes(const at::Tensor& planes, const at::Tensor& cu, int64_t max_len,
+                                                   int64_t H) {
+  check_qkv_planes(planes, H);
+  check_cuda(cu, "cu_seqlens");
+  TORCH_CHECK(cu.scalar_type() == at::kInt && cu.is_contiguous(), "cu_seqlens int32");
+  const int64_t T = planes.size(1), S = cu.numel() - 1;
+  c10::hip::HIPGuard g(planes.device().index());
+  auto out = at::empty({T, H * 128}, planes.options().dtype(at::kFloat));
+  auto lse = at::empty({H, T}, out.options());
+  if (T > 0 && S > 0)
+    as::varlen_attn_fwd_f32_planes(planes.data_ptr(), cu.data_ptr<int>(), out.data_ptr<float>(), lse.data_ptr<float>(),
+                                   S, max_len, H, T, 1.0f / std::sqrt(128.0f), stream());
+  return {out, lse};
+}
+
+at::Tensor varlen_attn_bwd_f32_planes(const at::Tensor& planes, const at::Tensor& out, const at::Tensor& dout,
+                                      const at::Tensor& lse, const at::Tensor& cu, int64_t max_len, int64_t H) {
+  check_qkv_planes(planes, H);
+  check_cuda(dout, "dout");
+  check_cuda(out, "out");
+  check_cuda(lse, "lse");
+  check_cuda(cu, "cu_seqlens");
+  const int64_t T = planes.size(1), S = cu.numel() - 1;
+  TORCH_CHECK(out.scalar_type() == at::kFloat && dout.scalar_type() == at::kFloat && out.dim() == 2 &&
+                  out.size(0) == T && out.size(1) == H * 128 && dout.sizes() == out.sizes() && dout.is_contiguous() &&
+                  out.is_contiguous(), "varlen_attn_bwd_f32_planes: out / dout fp32 [T, H*128]");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == H * T && lse.is_contiguous() &&
+                  cu.scalar_type() == at::kInt && cu.is_contiguous(), "varlen_attn_bwd_f32_planes: lse / cu_seqlens");
+  c10::hip::HIPGuard g(planes.device().index());
+  auto dqkv = at::empty({T, 3 * H * 128}, out.options());
+  auto delta = at::empty({H, T}, out.options());
+  if (T > 0 && S > 0)
+    as::varlen_attn_bwd_f32_planes(planes.data_ptr(), out.data_ptr<float>(), dout.data_ptr<float>(),
+                                   lse.data_ptr<float>(), cu.data_ptr<int>(), dqkv.data_ptr<float>(),
+                                   delta.data_ptr<float>(), S, max_len, H, T, 1.0f / std::sqrt(128.0f), stream());
   return dqkv;
 }
 
@@ -1041,6 +1102,46 @@ at::Tensor gemm_f32_psb(const at::Tensor& a, const at::Tensor& bsplit, int64_t N
   as::gemm_f32_psb(a.data_ptr<float>(), bsplit.data_ptr(), bp, rp, out.data_ptr<float>(), a.size(0),
                    static_cast<int>(N), static_cast<int>(K), static_cast<int>(act), static_cast<int>(variant), stream());
   return out;
+}
+
+bool gemm_f32_psb_planes_supported(int64_t M, int64_t N, int64_t K) {
+  return as::gemm_f32_psb_planes_supported(M, static_cast<int>(N), static_cast<int>(K));
+}
+
+// a [M, K] b^T + bias as its three bf16 parts: planes [3, M, N] of bf16 (part 0 + part 1 + part 2 == the fp32 value).
+// out: an existing contiguous bf16 buffer of at least 3 M N elements to write the planes into (its tail is left alone)
+at::Tensor gemm_f32_psb_planes(const at::Tensor& a, const at::Tensor& bsplit, int64_t N, int64_t K,
+                               const c10::optional<at::Tensor>& bias, int64_t variant,
+                               const c10::optional<at::Tensor>& out) {
+  check_cuda(a, "a");
+  check_cuda(bsplit, "bsplit");
+  TORCH_CHECK(a.scalar_type() == at::kFloat && a.dim() == 2 && a.size(1) == K && a.is_contiguous(),
+              "gemm_f32_psb_planes: contiguous fp32 a [M, K]");
+  TORCH_CHECK(bsplit.scalar_type() == at::kByte && bsplit.numel() == as::presplit_b_bytes(N, K) &&
+                  bsplit.is_contiguous(), "gemm_f32_psb_planes: bsplit must be presplit_b of an [N, K] matrix");
+  TORCH_CHECK(as::gemm_f32_psb_planes_supported(a.size(0), static_cast<int>(N), static_cast<int>(K)),
+              "gemm_f32_psb_planes: N % 128 == 0, K % 4 == 0, 6 M N < 2^31");
+  TORCH_CHECK(variant == 0 || variant == 1, "gemm_f32_psb_planes: variant 0 | 1");
+  const float* bp = nullptr;
+  if (bias && bias->defined()) {
+    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->numel() == N && bias->is_contiguous(),
+                "gemm_f32_psb_planes: bias");
+    bp = bias->data_ptr<float>();
+  }
+  const int64_t M = a.size(0);
+  c10::hip::HIPGuard g(a.device().index());
+  at::Tensor planes;
+  if (out && out->defined()) {
+    TORCH_CHECK(out->is_cuda() && out->scalar_type() == at::kBFloat16 && out->is_contiguous() &&
+                    out->numel() >= 3 * M * N && out->device() == a.device(),
+                "gemm_f32_psb_planes: out must be a contiguous bf16 buffer of >= 3 M N elements");
+    planes = *out;
+  } else {
+    planes = at::empty({3, M, N}, a.options().dtype(at::kBFloat16));
+  }
+  as::gemm_f32_psb_planes(a.data_ptr<float>(), bsplit.data_ptr(), bp, planes.data_ptr(), M, static_cast<int>(N),
+                          static_cast<int>(K), static_cast<int>(variant), stream());
+  return planes;
 }
 
 // log-probability of the taken action per head in one launch: logits[h] [..., C_h] (fp32 / bf16, contiguous),
@@ -2681,6 +2782,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cin"));
   m.def("gemm_f32_psb", &gemm_f32_psb, py::arg("a"), py::arg("bsplit"), py::arg("N"), py::arg("K"),
         py::arg("bias") = py::none(), py::arg("res") = py::none(), py::arg("act") = 0, py::arg("variant") = 0);
+  m.def("gemm_f32_psb_planes_supported", &gemm_f32_psb_planes_supported);
+  m.def("gemm_f32_psb_planes", &gemm_f32_psb_planes, py::arg("a"), py::arg("bsplit"), py::arg("N"), py::arg("K"),
+        py::arg("bias") = py::none(), py::arg("variant") = 1, py::arg("out") = py::none());
+  m.def("varlen_attn_planes_supported", &varlen_attn_planes_supported);
   m.def("entity_pack", &entity_pack);
   m.def("embed_relu_fwd", &embed_relu_fwd);
   m.def("embed_relu_bwd", &embed_relu_bwd, py::arg("dout"), py::arg("out"), py::arg("idx"), py::arg("V"),

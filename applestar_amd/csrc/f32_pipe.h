@@ -385,5 +385,59 @@ __device__ __forceinline__ void store_tile_staged(const f16v (&acc)[C::FM][C::FN
   }
 }
 
+// store_tile_staged with the output emitted as its three bf16 parts: the 8 columns a thread finishes (after the
+// bias) are one split8 unit, written as 16 B into each of three row-major planes [3][M][N] of bf16 (plane p at
+// planes + p M N 2 bytes), so a consumer that feeds split MFMAs reads its operands without splitting them again
+// (p0 + p1 + p2 == the fp32 value).  N % 8 == 0; rows >= M are not written.
+template <class C>
+__device__ __forceinline__ void store_tile_staged_planes(const f16v (&acc)[C::FM][C::FN], char* lds,
+                                                         char* __restrict__ planes, const float* __restrict__ bias,
+                                                         long M, int N, long m0, int n0) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid / C::WN, wn = wid % C::WN;
+  const int l32 = lane & 31, h = lane >> 5;
+  constexpr int G = C::BN / 4;
+  constexpr int CPR = C::BN / 8;
+  float* t = reinterpret_cast<float*>(lds);
+  const long plane = M * N * 2;
+#pragma unroll 1
+  for (int pass = 0; pass < C::WM * C::FM; ++pass) {
+    const int pw = pass / C::FM, pi = pass % C::FM;
+    __syncthreads();
+    if (wm == pw) {
+#pragma unroll
+      for (int i = 0; i < C::FM; ++i) {
+        if (i != pi) continue;
+#pragma unroll
+        for (int j = 0; j < C::FN; ++j)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int gr = (wn * C::TN + 32 * j + 8 * g + 4 * h) / 4;
+            *reinterpret_cast<float4*>(t + (l32 * G + (gr ^ (l32 % G))) * 4) =
+                make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+          }
+      }
+    }
+    __syncthreads();
+    for (int c = tid; c < 32 * CPR; c += C::NT) {
+      const int r = c / CPR, cc = c % CPR;
+      const long m = m0 + pw * C::TM + 32 * pi + r;
+      const int n = n0 + 8 * cc;
+      if (m >= M || n >= N) continue;
+      const float4 u0 = *reinterpret_cast<const float4*>(t + (r * G + ((2 * cc) ^ (r % G))) * 4);
+      const float4 u1 = *reinterpret_cast<const float4*>(t + (r * G + ((2 * cc + 1) ^ (r % G))) * 4);
+      float v[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
+      if (bias) {
+        const float4 b0 = *reinterpret_cast<const float4*>(bias + n), b1 = *reinterpret_cast<const float4*>(bias + n + 4);
+        v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
+      }
+      const Split3 s = split8(v);
+      char* o = planes + (m * N + n) * 2;
+#pragma unroll
+      for (int p = 0; p < 3; ++p) *reinterpret_cast<u32v4*>(o + p * plane) = s.p[p];
+    }
+  }
+}
+
 }  // namespace pipe
 }  // namespace as

@@ -176,6 +176,15 @@ void varlen_attn_fwd_f32(const float* qkv, const int* cu, float* out, float* lse
 int attn_f32_variant(int v);
 void varlen_attn_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse2, const int* cu,
                          float* dqkv, float* delta, int S, int max_len, int H, long Ttot, float scale, hipStream_t s);
+// The split path of the two above on qkv given as the bf16 planes [3][Ttot][3 H 128] of gemm_f32_psb_planes (the
+// image kernels with the staging split replaced by a copy): the same products in the same order, so out / lse2 /
+// dqkv equal the default fp32-qkv variant bit for bit.  Needs split-MFMA mode and varlen_attn_planes_supported.
+bool varlen_attn_planes_supported(int H, long Ttot);
+void varlen_attn_fwd_f32_planes(const void* planes, const int* cu, float* out, float* lse2, int S, int max_len, int H,
+                                long Ttot, float scale, hipStream_t s);
+void varlen_attn_bwd_f32_planes(const void* planes, const float* out, const float* dout, const float* lse2,
+                                const int* cu, float* dqkv, float* delta, int S, int max_len, int H, long Ttot,
+                                float scale, hipStream_t s);
 
 }  // namespace as
 
@@ -387,6 +396,11 @@ struct PresplitArgs {                    // passed by value (~1.6 KB of kernel a
 void multi_presplit(const PresplitArgs& a, hipStream_t s);
 void gemm_f32_psb(const float* a, const void* bsplit, const float* bias, const float* res, float* out, long M, int N,
                   int K, int act, int variant, hipStream_t s);
+// the same product (bias only, variant 0 / 1) written as the three bf16 parts of the result: row-major planes
+// [3][M][N] of bf16, part p of element (m, n) at plane p (p0 + p1 + p2 == the fp32 value, split_mfma.h)
+bool gemm_f32_psb_planes_supported(long M, int N, int K);
+void gemm_f32_psb_planes(const float* a, const void* bsplit, const float* bias, void* planes, long M, int N, int K,
+                         int variant, hipStream_t s);
 // 3 x 3 conv on the pre-split planes of w [Cout, 3, 3, Cin] (presplit_b of its [Cout, 9 Cin] view); res2 / mask:
 // the input-gradient epilogue extras of conv3x3_f32_fwd_epi2 (nullptr: off).  conv3x3_f32_psb picks the kernel -
 // halo window, LDS ring or register-streamed planes: the predicate, the switches (conv_halo_f32_mode,

@@ -24,6 +24,7 @@
 #include "../common.h"
 #include "../kernels.h"
 #include "../split_mfma.h"
+#include "../f32_pipe.h"
 
 namespace as {
 namespace {
@@ -829,6 +830,326 @@ __global__ __launch_bounds__(256, 2) void attn_f32_bwd_dkdv_img_kernel(
   }
 }
 
+// ---- qkv given as bf16 planes.  The image kernels above split every K / V (Q) block again in each of the up to
+// eight 64-row workgroups of a sequence, in three kernels, and the staging registers kept the next block from being
+// prefetched.  qkv is the output of one GEMM whose epilogue finishes exactly one split8 unit per thread
+// (gemm_f32_psb_planes), so here it arrives already split: planes [3][Ttot][3 H 128] of bf16, one head's 128 dims
+// of a token 256 contiguous bytes per plane.  Staging a block is then a copy by LDS-DMA (f32_pipe.h dma16: one
+// wave instruction fills 1 KB = 4 image rows of a plane; the image's chunk XOR rides on the per-lane SOURCE column,
+// rows at or past the sequence end take an out-of-range offset and land as zeros), with no staging registers, so
+// the next block streams in behind the MFMAs.  The LDS images, the fragment reads and the order of every product
+// are those of the image kernels: out / lse / dqkv are bit for bit those of the default variant.  dO stays fp32
+// (split while staged / in the dQ fragment), delta comes from fp32 o and dO.
+struct PlaneSrc {
+  pipe::i32x4 r;   // buffer resource over the three planes
+  int plb;         // bytes per plane (Ttot rows)
+  int rowb;        // bytes per token row of a plane: 3 H 256
+};
+
+// DMA of image rows r0 .. r0 + 31 (>= len: zeros).  base: plane-0 byte offset of (the sequence's first token, the
+// operand's head columns) plus this lane's piece column 16 ((lane & 15) ^ f(row)); wave w fills rows 4 w + (lane >> 4)
+// and + 16 of each plane
+__device__ __forceinline__ void plane_stage(char* img, const PlaneSrc& ps, int base, int r0, int len) {
+  const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int rl = 4 * w + ((threadIdx.x & 63) >> 4);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = r0 + rl + 16 * i;
+    const bool ok = r < len;
+    const int off = base + r * ps.rowb;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+      pipe::dma16(ps.r, img + pl * PLANE + (w + 4 * i) * 1024, ok ? off + pl * ps.plb : kOOB);
+  }
+}
+
+__device__ __forceinline__ int plane_lane_col() {
+  const int l = threadIdx.x & 63, rl = 4 * static_cast<int>(threadIdx.x >> 6) + (l >> 4);
+  return 16 * ((l & 15) ^ ((2 * (rl & 7)) | ((rl >> 3) & 1)));
+}
+
+// the split register fragment (dims 32 lg + 8 c + t) of one token's head row: p = part 0 of dim 32 lg of a valid
+// (clamped) row; !ok: zeros
+__device__ __forceinline__ void plane_frag(Split3 (&fs)[4], const char* __restrict__ p, int plb, bool ok) {
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const u32v4 v = *reinterpret_cast<const u32v4*>(p + static_cast<long>(pl) * plb + 16 * c);
+      fs[c].p[pl] = ok ? v : u32v4{0u, 0u, 0u, 0u};
+    }
+}
+
+__device__ __forceinline__ PlaneSrc plane_src(const char* planes, int H, long Ttot) {
+  PlaneSrc ps;
+  ps.rowb = 3 * H * 256;
+  ps.plb = static_cast<int>(Ttot * ps.rowb);
+  ps.r = pipe::rsrc(planes, 3L * ps.plb);
+  return ps;
+}
+
+// Forward.  K and V land half a block apart: V(kb) streams in behind S = K Q^T and the softmax, K(kb + 1) behind
+// P V - two barriers per block as before, no load in front of either.
+__global__ __launch_bounds__(256, 3) void attn_f32_fwd_pl_kernel(const char* __restrict__ planes,
+                                                                 const int* __restrict__ cu, float* __restrict__ out,
+                                                                 float* __restrict__ lse2, int H, long Ttot,
+                                                                 float scale_log2, int QB, int S) {
+  __shared__ __attribute__((aligned(16))) char K_i[IMG];
+  __shared__ __attribute__((aligned(16))) char V_i[IMG];
+  int qb, s, h;
+  if (!attn_item(QB, S, H, qb, s, h)) return;
+  const int start = cu[s];
+  const int len = cu[s + 1] - start;
+  if (qb * BR >= len) return;
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, lr = l & 15, lg = l >> 4;
+  const int HD = H * D;
+  const PlaneSrc ps = plane_src(planes, H, Ttot);
+  const int kbase = start * ps.rowb + (HD + h * D) * 2 + plane_lane_col(), vbase = kbase + HD * 2;
+  const int qrow = qb * BR + w * 16 + lr;
+  plane_stage(K_i, ps, kbase, 0, len);
+  Split3 qs[4];
+  plane_frag(qs, planes + (static_cast<long>(start) + (qrow < len ? qrow : 0)) * ps.rowb + (h * D + 32 * lg) * 2, ps.plb,
+             qrow < len);
+  f4 o[8];
+#pragma unroll
+  for (int n = 0; n < 8; ++n) o[n] = f4{0.f, 0.f, 0.f, 0.f};
+  float m = -1e30f, lsum = 0.f;
+  const int nkb = (len + IR - 1) / IR;
+  pipe::wait_vm<0>();
+  __syncthreads();
+  plane_stage(V_i, ps, vbase, 0, len);
+  for (int kb = 0; kb < nkb; ++kb) {
+    f4 st[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) st[n] = img_row_dot(K_i, n, qs);
+    float mx = -1e30f;
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float v = kb * IR + 16 * n + 4 * lg + i < len ? st[n][i] * scale_log2 : -1e30f;
+        st[n][i] = v;
+        mx = fmaxf(mx, v);
+      }
+    const float mn = fmaxf(m, xor_max(mx));
+    const float alpha = ex2(m - mn);
+    m = mn;
+    float rs = 0.f;
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float p = ex2(st[n][i] - mn);
+        st[n][i] = p;
+        rs += p;
+      }
+    lsum = lsum * alpha + xor_sum(rs);
+    const Split3 sp = split_pair_regs(st[0], st[1]);
+    pipe::wait_vm<0>();      // V(kb) landed
+    __syncthreads();         // ... in every wave, and every wave finished reading K(kb)
+    if (kb + 1 < nkb) plane_stage(K_i, ps, kbase, (kb + 1) * IR, len);
+#pragma unroll
+    for (int nd = 0; nd < 8; ++nd) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[nd][i] *= alpha;
+      o[nd] = mfma16_x6(img_tr(V_i, nd), sp, o[nd]);
+    }
+    if (kb + 1 < nkb) {
+      pipe::wait_vm<0>();    // K(kb + 1) landed
+      __syncthreads();       // ... and every wave finished reading V(kb)
+      plane_stage(V_i, ps, vbase, (kb + 1) * IR, len);
+    }
+  }
+  if (qrow < len) {
+    const float inv = 1.f / lsum;
+    float* dst = out + (static_cast<long>(start) + qrow) * HD + h * D + 4 * lg;
+#pragma unroll
+    for (int nd = 0; nd < 8; ++nd)
+      *reinterpret_cast<float4*>(dst + 16 * nd) = make_float4(o[nd][0] * inv, o[nd][1] * inv, o[nd][2] * inv,
+                                                              o[nd][3] * inv);
+    if (lg == 0) lse2[static_cast<long>(h) * Ttot + start + qrow] = m + log2f(lsum);
+  }
+}
+
+// dQ + delta.  K is read at both ends of a block (S, then K^T dS), V only in the middle: two K images (72 KB, two
+// workgroups per CU) take K(kb + 1) from the top of block kb, V(kb + 1) follows once dP is done.
+__global__ __launch_bounds__(256, 2) void attn_f32_bwd_dq_pl_kernel(
+    const char* __restrict__ planes, const float* __restrict__ o, const float* __restrict__ dout,
+    const float* __restrict__ lse2, float* __restrict__ delta, const int* __restrict__ cu, float* __restrict__ dqkv,
+    int H, long Ttot, float scale_log2, float scale, int QB, int S) {
+  __shared__ __attribute__((aligned(16))) char K_i[2 * IMG];
+  __shared__ __attribute__((aligned(16))) char V_i[IMG];
+  int qb, s, h;
+  if (!attn_item(QB, S, H, qb, s, h)) return;
+  const int start = cu[s];
+  const int len = cu[s + 1] - start;
+  if (qb * BR >= len) return;
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, lr = l & 15, lg = l >> 4;
+  const int HD = H * D;
+  const PlaneSrc ps = plane_src(planes, H, Ttot);
+  const int kbase = start * ps.rowb + (HD + h * D) * 2 + plane_lane_col(), vbase = kbase + HD * 2;
+  const float* dseq = dout + static_cast<long>(start) * HD;
+  const int qrow = qb * BR + w * 16 + lr;
+  const bool rval = qrow < len;
+  const int qr = rval ? qrow : 0;
+  plane_stage(K_i, ps, kbase, 0, len);
+  plane_stage(V_i, ps, vbase, 0, len);
+  Split3 qs[4], ds[4];
+  float dl = 0.f;
+  plane_frag(qs, planes + (static_cast<long>(start) + qr) * ps.rowb + (h * D + 32 * lg) * 2, ps.plb, rval);
+  {
+    float df[32];
+    load_row32(df, dseq + static_cast<long>(qr) * HD + h * D + 32 * lg, rval);
+    const float4* orow = reinterpret_cast<const float4*>(o + (static_cast<long>(start) + qr) * HD + h * D + 32 * lg);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float4 v = orow[q];   // clamped row; df is zero when !rval
+      dl += v.x * df[4 * q] + v.y * df[4 * q + 1] + v.z * df[4 * q + 2] + v.w * df[4 * q + 3];
+    }
+    dl = xor_sum(dl);
+    split_frag(df, ds);
+  }
+  const float ls = rval ? lse2[static_cast<long>(h) * Ttot + start + qrow] : 1e30f;
+  if (rval && lg == 0) delta[static_cast<long>(h) * Ttot + start + qrow] = dl;
+  f4 dq[8];
+#pragma unroll
+  for (int n = 0; n < 8; ++n) dq[n] = f4{0.f, 0.f, 0.f, 0.f};
+  const int nkb = (len + IR - 1) / IR;
+  pipe::wait_vm<0>();
+  __syncthreads();
+  for (int kb = 0; kb < nkb; ++kb) {
+    const char* Kc = K_i + (kb & 1) * IMG;
+    // the other K image was last read in block kb - 1, before the barrier that closed it
+    if (kb + 1 < nkb) plane_stage(K_i + ((kb + 1) & 1) * IMG, ps, kbase, (kb + 1) * IR, len);
+    f4 st[2], dpp[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      st[n] = img_row_dot(Kc, n, qs);
+      dpp[n] = img_row_dot(V_i, n, ds);
+    }
+    if (kb + 1 < nkb) {
+      __syncthreads();       // every wave finished reading V(kb)
+      plane_stage(V_i, ps, vbase, (kb + 1) * IR, len);
+    }
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool kv = kb * IR + 16 * n + 4 * lg + i < len;
+        const float p = kv ? ex2(st[n][i] * scale_log2 - ls) : 0.f;
+        dpp[n][i] = p * (dpp[n][i] - dl);
+      }
+    const Split3 sd = split_pair_regs(dpp[0], dpp[1]);
+#pragma unroll
+    for (int nd = 0; nd < 8; ++nd) dq[nd] = mfma16_x6(img_tr(Kc, nd), sd, dq[nd]);
+    if (kb + 1 < nkb) {
+      pipe::wait_vm<0>();    // K(kb + 1) and V(kb + 1) landed
+      __syncthreads();       // ... in every wave, and every wave finished reading K(kb)
+    }
+  }
+  if (rval) {
+    float* dqp = dqkv + (static_cast<long>(start) + qrow) * 3 * HD + h * D + 4 * lg;
+#pragma unroll
+    for (int nd = 0; nd < 8; ++nd)
+      *reinterpret_cast<float4*>(dqp + 16 * nd) = make_float4(dq[nd][0] * scale, dq[nd][1] * scale,
+                                                              dq[nd][2] * scale, dq[nd][3] * scale);
+  }
+}
+
+// dK / dV.  Q blocks by DMA, dO blocks split while staged (img_load / img_store), both K and V fragments from the
+// planes (256 VGPRs, nothing spilled; the fp32 form spills 17).  Measured and removed: the next block prefetched (two
+// Q images + dO in 16 registers): 984 us against 966 us for the backward at the learner's shape.
+__global__ __launch_bounds__(256, 2) void attn_f32_bwd_dkdv_pl_kernel(
+    const char* __restrict__ planes, const float* __restrict__ dout, const float* __restrict__ lse2,
+    const float* __restrict__ delta, const int* __restrict__ cu, float* __restrict__ dqkv, int H, long Ttot,
+    float scale_log2, float scale, int QB, int S) {
+  __shared__ __attribute__((aligned(16))) char Q_i[IMG];
+  __shared__ __attribute__((aligned(16))) char O_i[IMG];
+  __shared__ float lse_s[IR], del_s[IR];
+  int kb, s, h;
+  if (!attn_item(QB, S, H, kb, s, h)) return;
+  const int start = cu[s];
+  const int len = cu[s + 1] - start;
+  if (kb * BR >= len) return;
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, lr = l & 15, lg = l >> 4;
+  const int HD = H * D;
+  const PlaneSrc ps = plane_src(planes, H, Ttot);
+  const int qbase = start * ps.rowb + h * D * 2 + plane_lane_col();
+  const float* dseq = dout + static_cast<long>(start) * HD;
+  const int key = kb * BR + w * 16 + lr;
+  const bool kval = key < len;
+  const int kr0 = kval ? key : 0;
+  plane_stage(Q_i, ps, qbase, 0, len);
+  Split3 ks[4], vs[4];
+  {
+    const char* krow = planes + (static_cast<long>(start) + kr0) * ps.rowb + (HD + h * D + 32 * lg) * 2;
+    plane_frag(ks, krow, ps.plb, kval);
+    plane_frag(vs, krow + HD * 2, ps.plb, kval);
+  }
+  f4 dk[8], dv[8];
+#pragma unroll
+  for (int n = 0; n < 8; ++n) { dk[n] = f4{0.f, 0.f, 0.f, 0.f}; dv[n] = f4{0.f, 0.f, 0.f, 0.f}; }
+  const int nrb = (len + IR - 1) / IR;
+  float4 orr[4];
+  float lse_r = 1e30f, del_r = 0.f;
+  auto load_block = [&](int rb) {
+    img_load(orr, dseq + h * D, HD, rb * IR, len);
+    if (tid < IR) {
+      const int r = rb * IR + tid;
+      lse_r = r < len ? lse2[static_cast<long>(h) * Ttot + start + r] : 1e30f;
+      del_r = r < len ? delta[static_cast<long>(h) * Ttot + start + r] : 0.f;
+    }
+  };
+  load_block(0);
+  for (int rb = 0; rb < nrb; ++rb) {
+    if (rb) {
+      __syncthreads();                       // every wave finished reading block rb - 1
+      plane_stage(Q_i, ps, qbase, rb * IR, len);
+      load_block(rb);
+    }
+    img_store(O_i, orr);
+    if (tid < IR) {
+      lse_s[tid] = lse_r;
+      del_s[tid] = del_r;
+    }
+    pipe::wait_vm<0>();                      // Q(rb) landed
+    __syncthreads();
+    f4 scp[2], dpp[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      f4 sc = img_row_dot(Q_i, n, ks);     // [i]: row 16 n + 4 lg + i, key lr
+      f4 dp = img_row_dot(O_i, n, vs);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int rl = 16 * n + 4 * lg + i;
+        const float p = kval ? ex2(sc[i] * scale_log2 - lse_s[rl]) : 0.f;   // padded rows: lse = +inf
+        sc[i] = p;
+        dp[i] = p * (dp[i] - del_s[rl]);
+      }
+      scp[n] = sc;
+      dpp[n] = dp;
+    }
+    const Split3 sp = split_pair_regs(scp[0], scp[1]);
+    const Split3 sd = split_pair_regs(dpp[0], dpp[1]);
+#pragma unroll
+    for (int nd = 0; nd < 8; ++nd) {
+      dv[nd] = mfma16_x6(img_tr(O_i, nd), sp, dv[nd]);
+      dk[nd] = mfma16_x6(img_tr(Q_i, nd), sd, dk[nd]);
+    }
+  }
+  if (kval) {
+    const long tok = static_cast<long>(start) + key;
+    float* dkp = dqkv + tok * 3 * HD + HD + h * D + 4 * lg;
+    float* dvp = dqkv + tok * 3 * HD + 2 * HD + h * D + 4 * lg;
+#pragma unroll
+    for (int nd = 0; nd < 8; ++nd) {
+      *reinterpret_cast<float4*>(dkp + 16 * nd) = make_float4(dk[nd][0] * scale, dk[nd][1] * scale,
+                                                              dk[nd][2] * scale, dk[nd][3] * scale);
+      *reinterpret_cast<float4*>(dvp + 16 * nd) = make_float4(dv[nd][0], dv[nd][1], dv[nd][2], dv[nd][3]);
+    }
+  }
+}
+
 }  // namespace
 
 // split-path variant (APPLESTAR_F32_ATTN_IMG, or attn_f32_variant() at run time).  Default 23 = images, forward at
@@ -851,9 +1172,31 @@ int attn_f32_variant(int v) {
   return old;
 }
 
-namespace {
+// every plane byte offset the kernels form fits the 32-bit buffer offset (below the out-of-range marker)
+bool varlen_attn_planes_supported(int H, long Ttot) {
+  return H > 0 && Ttot > 0 && 3L * Ttot * (3L * H * 256) < 0x7ffffff0L;
+}
 
-}  // namespace
+void varlen_attn_fwd_f32_planes(const void* planes, const int* cu, float* out, float* lse2, int S, int max_len, int H,
+                                long Ttot, float scale, hipStream_t s) {
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const int QB = (max_len + BR - 1) / BR;
+  const dim3 grid(static_cast<unsigned>((static_cast<long>(QB) * S * H + 7) / 8 * 8));
+  hipLaunchKernelGGL(attn_f32_fwd_pl_kernel, grid, dim3(256), 0, s, static_cast<const char*>(planes), cu, out, lse2, H,
+                     Ttot, scale_log2, QB, S);
+}
+
+void varlen_attn_bwd_f32_planes(const void* planes, const float* out, const float* dout, const float* lse2,
+                                const int* cu, float* dqkv, float* delta, int S, int max_len, int H, long Ttot,
+                                float scale, hipStream_t s) {
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const int QB = (max_len + BR - 1) / BR;
+  const dim3 grid(static_cast<unsigned>((static_cast<long>(QB) * S * H + 7) / 8 * 8));
+  const char* pl = static_cast<const char*>(planes);
+  hipLaunchKernelGGL(attn_f32_bwd_dq_pl_kernel, grid, dim3(256), 0, s, pl, out, dout, lse2, delta, cu, dqkv, H, Ttot,
+                     scale_log2, scale, QB, S);
+  hipLaunchKernelGGL(attn_f32_bwd_dkdv_pl_kernel, grid, dim3(256), 0, s, pl, dout, lse2, delta, cu, dqkv, H, Ttot, scale_log2, scale, QB, S);
+}
 
 void varlen_attn_fwd_f32(const float* qkv, const int* cu, float* out, float* lse2, int S, int max_len, int H, long Ttot,
                          float scale, hipStream_t s) {

@@ -138,12 +138,11 @@ __device__ __forceinline__ void psb_sb_loop(char* ring, const IssueA& issue_a, i
 
 // DB: two B register sets (the next K-step's fragments load during this step's MFMAs: 204 VGPRs, 2 waves / SIMD);
 // else one set, each fragment reloaded right after its last MFMA (3 waves / SIMD)
-template <bool STAGED, bool DB>
-__global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_psb_kernel(const float* __restrict__ a,
-                                                              const u32v4* __restrict__ bs, int KT,
-                                                              const float* __restrict__ bias,
-                                                              const float* __restrict__ res, float* __restrict__ out,
-                                                              long M, int N, int K, int act) {
+// PLANES: `out` is the three bf16 planes [3][M][N] of the result (pipe::store_tile_staged_planes; bias only)
+template <bool STAGED, bool DB, bool PLANES>
+__device__ __forceinline__ void gemm_f32_psb_body(const float* __restrict__ a, const u32v4* __restrict__ bs, int KT,
+                                                  const float* __restrict__ bias, const float* __restrict__ res,
+                                                  void* __restrict__ out, long M, int N, int K, int act) {
   // the staged epilogue reuses stage 0 for 32 x 128 floats (16 KB)
   using C = pipe::Cfg<kPsbBN, kPsbNS, 16, kPsbBM, 4>;
   // one ring array (stage = kt % 3, addressed at run time: the DMA is inline asm, so the compiler adds no waits
@@ -262,11 +261,32 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_psb_kernel(const flo
     }
   }
   pipe::wait_vm<0>();
-  if constexpr (STAGED) {
-    pipe::store_tile_staged<C, float>(acc, ring, out, bias, res, M, N, m0, n0, act);
+  if constexpr (PLANES) {
+    pipe::store_tile_staged_planes<C>(acc, ring, static_cast<char*>(out), bias, M, N, m0, n0);
+  } else if constexpr (STAGED) {
+    pipe::store_tile_staged<C, float>(acc, ring, static_cast<float*>(out), bias, res, M, N, m0, n0, act);
   } else {
-    pipe::store_tile<C::FM, 2>(acc, out, bias, res, M, N, m0 + wm * C::TM, n0 + wn * C::TN, act);
+    pipe::store_tile<C::FM, 2>(acc, static_cast<float*>(out), bias, res, M, N, m0 + wm * C::TM, n0 + wn * C::TN, act);
   }
+}
+
+template <bool STAGED, bool DB>
+__global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_psb_kernel(const float* __restrict__ a,
+                                                              const u32v4* __restrict__ bs, int KT,
+                                                              const float* __restrict__ bias,
+                                                              const float* __restrict__ res, float* __restrict__ out,
+                                                              long M, int N, int K, int act) {
+  gemm_f32_psb_body<STAGED, DB, false>(a, bs, KT, bias, res, out, M, N, K, act);
+}
+
+// the same product with the output written as bf16 planes (the QKV projection feeding attention_f32.hip)
+template <bool DB>
+__global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_psb_planes_kernel(const float* __restrict__ a,
+                                                                     const u32v4* __restrict__ bs, int KT,
+                                                                     const float* __restrict__ bias,
+                                                                     void* __restrict__ planes, long M, int N,
+                                                                     int K) {
+  gemm_f32_psb_body<true, DB, true>(a, bs, KT, bias, nullptr, planes, M, N, K, 0);
 }
 
 // 3 x 3 / pad 1 convolution (NHWC x [B, H, W, Cin], Cout % 128 == 0, Cin % 16 == 0) on the pre-split weight planes
@@ -356,6 +376,25 @@ void gemm_f32_psb(const float* a, const void* bsplit, const float* bias, const f
   else
     hipLaunchKernelGGL((gemm_f32_psb_kernel<true, true>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, s, a,
                        static_cast<const u32v4*>(bsplit), KT, bias, res, out, M, N, K, act);
+}
+
+// gemm_f32_psb's shapes, and the three planes below 2^31 bytes (their consumer addresses them with 32-bit offsets)
+bool gemm_f32_psb_planes_supported(long M, int N, int K) {
+  return gemm_f32_psb_supported(M, N, K) && 3 * M * N * 2 < 0x7ffffff0L;
+}
+
+// planes = the bf16 planes [3][M][N] of A B^T + bias (split8 of every 8 finished columns); variant 0 / 1 as above
+void gemm_f32_psb_planes(const float* a, const void* bsplit, const float* bias, void* planes, long M, int N, int K,
+                         int variant, hipStream_t s) {
+  const long nwg = (M + kPsbBM - 1) / kPsbBM * (N / kPsbBN);
+  if (nwg == 0) return;
+  const int KT = (K + 15) / 16;
+  if (variant == 1)
+    hipLaunchKernelGGL((gemm_f32_psb_planes_kernel<false>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, s, a,
+                       static_cast<const u32v4*>(bsplit), KT, bias, planes, M, N, K);
+  else
+    hipLaunchKernelGGL((gemm_f32_psb_planes_kernel<true>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, s, a,
+                       static_cast<const u32v4*>(bsplit), KT, bias, planes, M, N, K);
 }
 
 // conv3x3_f32_psb_kernel: Cout % 128 == 0 (which conv takes it: conv3x3_f32_dispatch.hip)

@@ -92,9 +92,9 @@ class TransformerLayer(nn.Module):
         assert self.ln_type == 'post'
         link1, link2 = ops.grad_link(x), ops.grad_link(x)
         pre = self.attention.attention_pre[0]
-        qkv = ops.linear(x, pre.weight, pre.bias, grad_link=link1)
-        a = self.attention.project(ops.varlen_attention(qkv, cu_seqlens, max_len, self.attention.head_num,
-                                                        self.attention.head_dim))
+        a = self.attention.project(ops.qkv_attention(x, pre.weight, pre.bias, cu_seqlens, max_len,
+                                                     self.attention.head_num, self.attention.head_dim,
+                                                     grad_link=link1))
         x = ops.layer_norm(a, self.layernorm1.weight, self.layernorm1.bias, residual=x, grad_link=link1)
         fc0 = self.mlp[0]
         m = ops.linear(x, fc0[0].weight, fc0[0].bias, act='relu' if fc0.act else None, grad_link=link2)

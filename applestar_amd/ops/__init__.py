@@ -23,6 +23,7 @@ from . import _ext
 from .native import set_deterministic, deterministic
 
 __all__ = ['linear', 'layer_norm', 'conv2d', 'max_pool2x2', 'segment_sum', 'gather_rows', 'embed_relu', 'gated_residual', 'lnlstm_layer', 'varlen_attention',
+           'qkv_attention',
            'masked_attention', 'scatter_connection', 'sequence_mask', 'native_enabled', 'set_native', 'set_deterministic',
            'deterministic', 'gather_steps', 'index_rows', 'upsample2x',
            'upsample_conv_out', 'head_sample', 'target_unit_sample']
@@ -184,6 +185,17 @@ def varlen_attention(qkv, cu_seqlens, max_len: int, num_heads: int, head_dim: in
     if n is not None and n.has('varlen_attention'):
         return n.varlen_attention(qkv, cu_seqlens, max_len, num_heads, head_dim)
     return ref.varlen_attention(qkv, cu_seqlens, max_len, num_heads, head_dim)
+
+
+def qkv_attention(x, w, b, cu_seqlens, max_len: int, num_heads: int, head_dim: int, grad_link=None):
+    """varlen_attention(linear(x, w, b)) over packed tokens x [T, K].  GPU: the fp32 training step keeps qkv as
+    bf16 planes between the two kernels (native.qkv_attention); every other case runs the two ops."""
+    n = _native(x)
+    if n is not None and n.has('varlen_attention'):
+        return n.qkv_attention(x, w, b, cu_seqlens, max_len, num_heads, head_dim, grad_link=grad_link)
+    if n is not None:
+        return varlen_attention(linear(x, w, b, grad_link=grad_link), cu_seqlens, max_len, num_heads, head_dim)
+    return ref.qkv_attention(x, w, b, cu_seqlens, max_len, num_heads, head_dim)
 
 
 def action_logp(logits, actions):

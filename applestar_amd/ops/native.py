@@ -581,6 +581,65 @@ def varlen_attention(qkv, cu_seqlens, max_len: int, num_heads: int, head_dim: in
     return _VarlenAttention.apply(qkv.contiguous(), cu, int(max_len), int(num_heads))
 
 
+# QKV projection + fp32 varlen attention with qkv kept as bf16 planes (gemm_f32_psb_planes -> the plane kernels of
+# attention_f32.hip): the attention kernels copy their K / V / Q blocks instead of splitting them in every 64-row
+# workgroup.  APPLESTAR_ATTN_QKV_PLANES=0: the separate linear + attention launches.
+ATTN_QKV_PLANES = os.environ.get('APPLESTAR_ATTN_QKV_PLANES', '1') == '1'
+
+
+class _QKVAttention(torch.autograd.Function):
+    """out = varlen_attention(x2 W^T + b): the projection writes the three bf16 parts of qkv, which is all the
+    attention kernels read (and all that is saved); backward = the plane dQ / dK/dV kernels, then the backward of
+    the linear as :class:`_Linear` runs it (``_linear_bwd``)."""
+
+    @staticmethod
+    def forward(ctx, x2, w, b, cu, max_len, heads, link=None):
+        _count_use(w)
+        N, K = w.shape
+        planes = _C.gemm_f32_psb_planes(x2, _psb(w), N, K, _w32(b) if b is not None else None, GEMM_PSB_VARIANT)
+        out, lse = _C.varlen_attn_fwd_f32(planes, cu, max_len, heads)
+        ctx.save_for_backward(x2, w, planes, out, lse, cu)
+        ctx.max_len, ctx.heads = max_len, heads
+        ctx.link, ctx.relu = link, False
+        ctx.b_dtype = b.dtype if b is not None else None
+        ctx.mask_in = link is None and _relu_src(x2)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, w, planes, out, lse, cu = ctx.saved_tensors
+        dqkv = _C.varlen_attn_bwd_f32(planes, out, dout.float().contiguous(), lse, cu, ctx.max_len, ctx.heads)
+        return _linear_bwd(ctx, dqkv, x2, w, None)[:3] + (None, None, None, None)
+
+
+def _qkv_planes_ok(x, w, b, R, num_heads, head_dim):
+    """The packed fp32 training path whose projection :class:`_Linear` would run on gemm_f32_psb (the conditions of
+    :func:`linear`'s fp32 branch and of that node's pre-split branch), in split-MFMA mode, 32-bit plane offsets."""
+    if w.dim() != 2:
+        return False
+    N, K = w.shape
+    return ATTN_QKV_PLANES and head_dim == 128 and N == 3 * num_heads * head_dim and x.is_cuda and x.dim() == 2 and \
+        x.dtype == torch.float32 and w.dtype == torch.float32 and (b is None or b.dtype == torch.float32) and \
+        not torch.is_autocast_enabled() and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad) and \
+        R >= _WGRAD_MIN_ROWS and K % 4 == 0 and K <= F32_SMALL_K_MAX and R * max(N, K) * 4 < 0x7ffffff0 and \
+        GEMM_PSB_VARIANT in (0, 1) and _gemm_f32_ok(R, N, K) and _psb_ok(R, N, K) and \
+        _C.gemm_f32_psb_planes_supported(R, N, K) and _C.varlen_attn_planes_supported(num_heads, R)
+
+
+def qkv_attention(x, w, b, cu_seqlens, max_len: int, num_heads: int, head_dim: int, grad_link=None):
+    """varlen_attention(linear(x, w, b)) over packed tokens x [T, K].  The fp32 training step in split-MFMA mode
+    takes :class:`_QKVAttention` (qkv as bf16 planes); everything else the two separate ops."""
+    ensure_loaded()
+    if not _qkv_planes_ok(x, w, b, x.shape[0] if x.dim() == 2 else 0, num_heads, head_dim):
+        return varlen_attention(linear(x, w, b, grad_link=grad_link), cu_seqlens, max_len, num_heads, head_dim)
+    link = None
+    if grad_link is not None and RESID_LINK and x.is_contiguous() and x.requires_grad:
+        grad_link.armed, link, x2 = x, grad_link, x
+    else:
+        x2 = x.contiguous()
+    return _QKVAttention.apply(x2, w, b, cu_seqlens.to(torch.int32).contiguous(), int(max_len), int(num_heads), link)
+
+
 def linear_f32_rows(x, w, b=None):
     """fp32 x W^T + b without autograd (inference): the native f32 GEMM when it takes the shape (few rows: one wave
     per 32 x 32 tile), else torch.addmm; the weight / bias read as fp32 derived forms."""
@@ -2046,77 +2105,82 @@ class _Linear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w, y = ctx.saved_tensors
-        if ctx.relu and y.dtype == torch.float32 and _premasked(y, dy):
-            dy = dy.contiguous().view(y.shape)      # the consumer's dX epilogue applied this ReLU's mask
-        elif ctx.relu:
-            R, N = y.shape
-            _premask_miss(ctx, 'linear', y)
-            dy = _act_grad(dy.view(1, 1, R, N) if dy.is_contiguous() else dy.contiguous().view(1, 1, R, N),
-                           y.view(1, 1, R, N), True).view(R, N)
+        return _linear_bwd(ctx, dy, *ctx.saved_tensors)
+
+
+def _linear_bwd(ctx, dy, x2, w, y):
+    """Backward of y = act(x2 W^T + b) for :class:`_Linear` and the nodes that end in one (``_QKVAttention``):
+    ``ctx`` carries relu / b_dtype / link / mask_in and needs_input_grad[0] for x2."""
+    if ctx.relu and y.dtype == torch.float32 and _premasked(y, dy):
+        dy = dy.contiguous().view(y.shape)      # the consumer's dX epilogue applied this ReLU's mask
+    elif ctx.relu:
+        R, N = y.shape
+        _premask_miss(ctx, 'linear', y)
+        dy = _act_grad(dy.view(1, 1, R, N) if dy.is_contiguous() else dy.contiguous().view(1, 1, R, N),
+                       y.view(1, 1, R, N), True).view(R, N)
+    else:
+        dy = dy.to(x2.dtype).contiguous()
+    has_b = ctx.b_dtype is not None
+    side = _SideWork(dy, dy.shape[0])
+    with side.fork():       # dW / db concurrent with the dX GEMM below
+        dw, db = _wgrad(dy, x2, 0, has_b, _bf16_grads(w.dtype, ctx.b_dtype), w)
+        dw = dw.to(w.dtype)
+        db = db.to(ctx.b_dtype) if has_b else None
+    dx = None
+    g = None
+    if ctx.link is not None:
+        g, ctx.link.g = ctx.link.g, None
+        if g is not None and (_Deferred.on or _Deferred.flushed is not None):
+            # g is written in place below; queued / side-stream weight gradients may still read it
+            defer_end(g.device)
+        if _DEBUG_GRADLINK and g is not None and g._version != ctx.link.version:
+            raise RuntimeError('GradLink: the handed-over residual gradient was modified before the dX GEMM')
+    if dy.dtype == torch.float32 and _gemm_f32_ok(dy.shape[0], w.shape[1], dy.shape[1]) and \
+            (g is not None or ctx.needs_input_grad[0]):
+        # fp32: dX = dY W (+ the handed-over residual gradient) on the f32-MFMA GEMM, out of place; when x is
+        # the ReLU output of another fp32 linear, that ReLU's mask is applied here (epilogue mode 4) and
+        # the producer's backward skips its own threshold pass (_premasked)
+        psb = w.dim() == 2 and _psb_ok(dy.shape[0], w.shape[1], dy.shape[1])
+        if g is None and ctx.mask_in:
+            dx = _C.gemm_f32_psb(dy, _psb(w, True), w.shape[1], w.shape[0], None, x2, 4, GEMM_PSB_VARIANT) if psb \
+                else _C.gemm_f32(dy, _wT(w), None, x2, 4)
+            _MASKED_DX[x2.data_ptr()] = (dx, dx._version)
         else:
-            dy = dy.to(x2.dtype).contiguous()
-        has_b = ctx.b_dtype is not None
-        side = _SideWork(dy, dy.shape[0])
-        with side.fork():       # dW / db concurrent with the dX GEMM below
-            dw, db = _wgrad(dy, x2, 0, has_b, _bf16_grads(w.dtype, ctx.b_dtype), w)
-            dw = dw.to(w.dtype)
-            db = db.to(ctx.b_dtype) if has_b else None
-        dx = None
-        g = None
-        if ctx.link is not None:
-            g, ctx.link.g = ctx.link.g, None
-            if g is not None and (_Deferred.on or _Deferred.flushed is not None):
-                # g is written in place below; queued / side-stream weight gradients may still read it
-                defer_end(g.device)
-            if _DEBUG_GRADLINK and g is not None and g._version != ctx.link.version:
-                raise RuntimeError('GradLink: the handed-over residual gradient was modified before the dX GEMM')
-        if dy.dtype == torch.float32 and _gemm_f32_ok(dy.shape[0], w.shape[1], dy.shape[1]) and \
-                (g is not None or ctx.needs_input_grad[0]):
-            # fp32: dX = dY W (+ the handed-over residual gradient) on the f32-MFMA GEMM, out of place; when x is
-            # the ReLU output of another fp32 linear, that ReLU's mask is applied here (epilogue mode 4) and
-            # the producer's backward skips its own threshold pass (_premasked)
-            psb = w.dim() == 2 and _psb_ok(dy.shape[0], w.shape[1], dy.shape[1])
-            if g is None and ctx.mask_in:
-                dx = _C.gemm_f32_psb(dy, _psb(w, True), w.shape[1], w.shape[0], None, x2, 4, GEMM_PSB_VARIANT) if psb \
-                    else _C.gemm_f32(dy, _wT(w), None, x2, 4)
-                _MASKED_DX[x2.data_ptr()] = (dx, dx._version)
-            else:
-                r = None if g is None else g.view(dy.shape[0], w.shape[1])
-                if psb and r is not None and not r.is_contiguous():
-                    psb = False
-                dx = _C.gemm_f32_psb(dy, _psb(w, True), w.shape[1], w.shape[0], None, r, 0, GEMM_PSB_VARIANT) if psb \
-                    else _C.gemm_f32(dy, _wT(w), None, r, 0)
-        elif (g is not None or ctx.needs_input_grad[0]) and _bf16_small_ok(dy, dy.shape[0], w.shape[1], dy.shape[1]) \
-                and (g is None or g.dtype == torch.bfloat16):
-            # bf16 step, few rows: dX = dY W (+ the handed-over residual gradient) on the small-tile kernel
-            dx = _C.gemm_bf16_small(dy.contiguous(), _wT(w), None,
-                                    None if g is None else g.view(dy.shape[0], w.shape[1]).contiguous(), 0)
-        elif (g is not None or ctx.needs_input_grad[0]) and _bf16_pipe_ok(dy, dy.shape[0], w.shape[1], dy.shape[1]) \
-                and (g is None or g.dtype == torch.bfloat16) and not (g is None and dy.shape[1] == 32):
-            # bf16 step, many rows: dX = dY W (+ the handed-over residual gradient) on the LDS-DMA ring kernel
-            dx = _C.gemm_bf16(dy.contiguous(), _wT(w), None,
-                              None if g is None else g.view(dy.shape[0], w.shape[1]).contiguous(), 0)
-        elif g is not None:
-            # + the residual gradient the closing LayerNorm handed over (GradLink), in the GEMM epilogue
-            # in place: g is the LayerNorm's input gradient, which the branch's later layers (backward
-            # runs earlier, same stream) have already consumed; out-of-place addmm copied g first
-            wt = _wT(w).t() if GEMM_REFORM and dy.shape[0] * w.shape[1] >= (1 << 22) else w
-            dx = g.view(dy.shape[0], w.shape[1]).addmm_(dy, wt)
-        elif ctx.needs_input_grad[0]:
-            if dy.shape[1] == 32 and x2.shape[1] % 16 == 0 and dy.is_contiguous() and dy.dtype == torch.bfloat16:
-                # thin-K product (the heads' 256 -> 32 key projections): one MFMA per output tile, a pure
-                # store stream (gemm_k32.hip); the library took 0.19 ms per 196k-row call
-                dx = _C.mm_k32(dy, _wT(w))
-            elif GEMM_REFORM and dy.shape[0] * w.shape[1] >= (1 << 22):
-                # dY W as an "NT" product against a transposed weight copy (the layout of the forward):
-                # hipBLASLt's "NN" kernels ran the transformer FFN dX at 132 vs 106 us and the value fc's
-                # 390 x 12160 dX at 32 vs 19 us (tools/bench_gemm_alts.py)
-                dx = torch.nn.functional.linear(dy, _wT(w))
-            else:
-                dx = torch.mm(dy, w)
-        side.join(dw, db)
-        return dx, dw, db, None, None
+            r = None if g is None else g.view(dy.shape[0], w.shape[1])
+            if psb and r is not None and not r.is_contiguous():
+                psb = False
+            dx = _C.gemm_f32_psb(dy, _psb(w, True), w.shape[1], w.shape[0], None, r, 0, GEMM_PSB_VARIANT) if psb \
+                else _C.gemm_f32(dy, _wT(w), None, r, 0)
+    elif (g is not None or ctx.needs_input_grad[0]) and _bf16_small_ok(dy, dy.shape[0], w.shape[1], dy.shape[1]) \
+            and (g is None or g.dtype == torch.bfloat16):
+        # bf16 step, few rows: dX = dY W (+ the handed-over residual gradient) on the small-tile kernel
+        dx = _C.gemm_bf16_small(dy.contiguous(), _wT(w), None,
+                                None if g is None else g.view(dy.shape[0], w.shape[1]).contiguous(), 0)
+    elif (g is not None or ctx.needs_input_grad[0]) and _bf16_pipe_ok(dy, dy.shape[0], w.shape[1], dy.shape[1]) \
+            and (g is None or g.dtype == torch.bfloat16) and not (g is None and dy.shape[1] == 32):
+        # bf16 step, many rows: dX = dY W (+ the handed-over residual gradient) on the LDS-DMA ring kernel
+        dx = _C.gemm_bf16(dy.contiguous(), _wT(w), None,
+                          None if g is None else g.view(dy.shape[0], w.shape[1]).contiguous(), 0)
+    elif g is not None:
+        # + the residual gradient the closing LayerNorm handed over (GradLink), in the GEMM epilogue
+        # in place: g is the LayerNorm's input gradient, which the branch's later layers (backward
+        # runs earlier, same stream) have already consumed; out-of-place addmm copied g first
+        wt = _wT(w).t() if GEMM_REFORM and dy.shape[0] * w.shape[1] >= (1 << 22) else w
+        dx = g.view(dy.shape[0], w.shape[1]).addmm_(dy, wt)
+    elif ctx.needs_input_grad[0]:
+        if dy.shape[1] == 32 and x2.shape[1] % 16 == 0 and dy.is_contiguous() and dy.dtype == torch.bfloat16:
+            # thin-K product (the heads' 256 -> 32 key projections): one MFMA per output tile, a pure
+            # store stream (gemm_k32.hip); the library took 0.19 ms per 196k-row call
+            dx = _C.mm_k32(dy, _wT(w))
+        elif GEMM_REFORM and dy.shape[0] * w.shape[1] >= (1 << 22):
+            # dY W as an "NT" product against a transposed weight copy (the layout of the forward):
+            # hipBLASLt's "NN" kernels ran the transformer FFN dX at 132 vs 106 us and the value fc's
+            # 390 x 12160 dX at 32 vs 19 us (tools/bench_gemm_alts.py)
+            dx = torch.nn.functional.linear(dy, _wT(w))
+        else:
+            dx = torch.mm(dy, w)
+    side.join(dw, db)
+    return dx, dw, db, None, None
 
 
 # ---------------------------------------------------------------------------- ReLU-mask hand-off (fp32 linears)

@@ -105,6 +105,11 @@ def varlen_attention(qkv, cu_seqlens, max_len: int, num_heads: int, head_dim: in
     return out[valid]
 
 
+def qkv_attention(x, w, b, cu_seqlens, max_len: int, num_heads: int, head_dim: int):
+    """Packed self-attention on the projection qkv = x W^T + b of the packed tokens x [T, K]."""
+    return varlen_attention(F.linear(x, w, b), cu_seqlens, max_len, num_heads, head_dim)
+
+
 def _pack_index(seqlens, max_len):
     ar = torch.arange(max_len, device=seqlens.device)
     valid = (ar[None, :] < seqlens[:, None]).reshape(-1)
