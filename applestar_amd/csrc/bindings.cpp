@@ -2632,6 +2632,56 @@ void multi_copy(const std::vector<at::Tensor>& dsts, const std::vector<at::Tenso
   flush();
 }
 
+// dst[i] = (dst[i] + src[i]) * scale (gradient accumulation over micro-batches): fp32 destinations, fp32 or bf16
+// sources, the pairs multi_copy takes natively in one launch per kCopyMaxT tensors; the rest add_ + mul_.  A source
+// of None adds nothing: its destination only takes the scale (a slot without a gradient in the closing micro-batch)
+void multi_accumulate(const std::vector<at::Tensor>& dsts, const std::vector<c10::optional<at::Tensor>>& srcs,
+                      double scale) {
+  TORCH_CHECK(dsts.size() == srcs.size(), "multi_accumulate: list sizes");
+  if (dsts.empty()) return;
+  c10::hip::HIPGuard g(dsts[0].device().index());
+  const float sc = static_cast<float>(scale);
+  as::CopyArgs a;
+  a.ntensors = 0;
+  a.chunk_start[0] = 0;
+  auto flush = [&]() {
+    if (a.ntensors > 0) as::multi_accumulate(a, sc, stream());
+    a.ntensors = 0;
+    a.chunk_start[0] = 0;
+  };
+  for (size_t i = 0; i < dsts.size(); ++i) {
+    const at::Tensor& d = dsts[i];
+    const bool has = srcs[i].has_value() && srcs[i]->defined();
+    TORCH_CHECK(d.is_cuda() && d.device() == dsts[0].device(), "multi_accumulate: GPU tensors on one device");
+    TORCH_CHECK(d.scalar_type() == at::kFloat, "multi_accumulate: fp32 destination (the accumulator is never bf16)");
+    bool ok = d.is_non_overlapping_and_dense();
+    if (has) {
+      const at::Tensor& s = *srcs[i];
+      TORCH_CHECK(s.is_cuda() && d.device() == s.device() && d.sizes() == s.sizes(),
+                  "multi_accumulate: GPU tensors of equal shape");
+      TORCH_CHECK(s.scalar_type() == at::kFloat || s.scalar_type() == at::kBFloat16,
+                  "multi_accumulate: fp32/bf16 source");
+      ok = ok && d.strides() == s.strides();
+    }
+    if (!ok) {
+      at::Tensor dd = d;
+      if (has) dd.add_(*srcs[i]);
+      dd.mul_(sc);
+      continue;
+    }
+    const long n = d.numel();
+    if (n == 0) continue;
+    const int t = a.ntensors++;
+    a.src[t] = has ? srcs[i]->data_ptr() : nullptr;
+    a.dst[t] = d.data_ptr();
+    a.n[t] = n;
+    a.dts[t] = static_cast<unsigned char>(!has ? (2 | 32) : ((srcs[i]->scalar_type() == at::kFloat ? 1 : 0) | 2));
+    a.chunk_start[t + 1] = a.chunk_start[t] + static_cast<int>((n + as::kCopyChunk - 1) / as::kCopyChunk);
+    if (a.ntensors == as::kCopyMaxT) flush();
+  }
+  flush();
+}
+
 // ---------------------------------------------------------------- strided multi-tensor copy (derived weight forms)
 // dsts[t] (contiguous, fp32/bf16) <- srcs[t] read through spec[9 t .. 9 t + 8] = {size0..3, stride0..3, base}
 // (element units, relative to srcs[t].data_ptr(); strides may be negative).  Every reachable source offset is
@@ -2675,8 +2725,9 @@ void col_sum(const std::vector<at::Tensor>& dsts, const std::vector<int64_t>& dc
   as::col_sum(a, stream());
 }
 
-void multi_strided_copy(const std::vector<at::Tensor>& dsts, const std::vector<at::Tensor>& srcs,
-                        const std::vector<int64_t>& spec) {
+// acc: dst = (dst + the element the copy would read) * scale (fp32 destinations only) instead of the copy
+static void strided_fill(const std::vector<at::Tensor>& dsts, const std::vector<at::Tensor>& srcs,
+                         const std::vector<int64_t>& spec, bool acc, float scale) {
   TORCH_CHECK(dsts.size() == srcs.size() && spec.size() == 9 * dsts.size(), "multi_strided_copy: list sizes");
   if (dsts.empty()) return;
   c10::hip::HIPGuard g(dsts[0].device().index());
@@ -2684,7 +2735,10 @@ void multi_strided_copy(const std::vector<at::Tensor>& dsts, const std::vector<a
   a.ntensors = 0;
   a.chunk_start[0] = 0;
   auto flush = [&]() {
-    if (a.ntensors > 0) as::multi_strided_copy(a, stream());
+    if (a.ntensors > 0) {
+      if (acc) as::multi_strided_accumulate(a, scale, stream());
+      else as::multi_strided_copy(a, stream());
+    }
     a.ntensors = 0;
     a.chunk_start[0] = 0;
   };
@@ -2695,6 +2749,8 @@ void multi_strided_copy(const std::vector<at::Tensor>& dsts, const std::vector<a
     TORCH_CHECK(d.is_contiguous(), "multi_strided_copy: contiguous destination");
     TORCH_CHECK((d.scalar_type() == at::kFloat || d.scalar_type() == at::kBFloat16) &&
                 (s.scalar_type() == at::kFloat || s.scalar_type() == at::kBFloat16), "multi_strided_copy: fp32/bf16");
+    TORCH_CHECK(!acc || d.scalar_type() == at::kFloat,
+                "multi_strided_accumulate: fp32 destination (the accumulator is never bf16)");
     const int64_t* sp = spec.data() + 9 * i;
     int64_t n = 1, lo = sp[8], hi = sp[8];
     for (int k = 0; k < 4; ++k) {
@@ -2718,7 +2774,8 @@ void multi_strided_copy(const std::vector<at::Tensor>& dsts, const std::vector<a
     a.base[t] = sp[8];
     // a transpose of the last two dims (dst rows contiguous in the source) of a large tensor: LDS-tiled path,
     // one 64 x 128 tile per block
-    const bool tiled = sp[0] == 1 && sp[1] == 1 && sp[6] == 1 && sp[7] > 1 && n >= (1 << 16);
+    // (accumulating, at every size: a transposed gradient of any size reads its source along the rows)
+    const bool tiled = sp[0] == 1 && sp[1] == 1 && sp[6] == 1 && sp[7] > 1 && (acc || n >= (1 << 16));
     a.dts[t] = static_cast<unsigned char>((s.scalar_type() == at::kFloat ? 1 : 0) | (d.scalar_type() == at::kFloat ? 2 : 0) |
                                           (tiled ? 4 : 0));
     const int64_t chunks = tiled ? ((sp[2] + 63) / 64) * ((sp[3] + 127) / 128) : (n + as::kCopyChunk - 1) / as::kCopyChunk;
@@ -2726,6 +2783,16 @@ void multi_strided_copy(const std::vector<at::Tensor>& dsts, const std::vector<a
     if (a.ntensors == as::kSCopyMaxT) flush();
   }
   flush();
+}
+
+void multi_strided_copy(const std::vector<at::Tensor>& dsts, const std::vector<at::Tensor>& srcs,
+                        const std::vector<int64_t>& spec) {
+  strided_fill(dsts, srcs, spec, false, 1.f);
+}
+
+void multi_strided_accumulate(const std::vector<at::Tensor>& dsts, const std::vector<at::Tensor>& srcs,
+                              const std::vector<int64_t>& spec, double scale) {
+  strided_fill(dsts, srcs, spec, true, static_cast<float>(scale));
 }
 
 // ---------------------------------------------------------------- narrow 1x1 conv on NHWC pixels
@@ -2869,6 +2936,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("multi_copy", &multi_copy);
   m.def("ln_affine_grads", &ln_affine_grads);
   m.def("multi_strided_copy", &multi_strided_copy);
+  m.def("multi_accumulate", &multi_accumulate);
+  m.def("multi_strided_accumulate", &multi_strided_accumulate);
   m.def("loc_in_fwd", &loc_in_fwd);
   m.def("vsp_fwd", &vsp_fwd);
   m.def("rl_loss", &rl_loss, py::arg("alp"), py::arg("blp"), py::arg("hm"), py::arg("ent"), py::arg("kl"), py::arg("v"),

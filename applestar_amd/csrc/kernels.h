@@ -343,9 +343,14 @@ struct CopyArgs {                     // passed by value (< 2 KB of kernel argum
   void* dst[kCopyMaxT];
   long n[kCopyMaxT];                  // elements (raw: bytes)
   unsigned char dts[kCopyMaxT];       // bit 0: src fp32, bit 1: dst fp32 (else bf16), bit 2: raw bytes, same dtype,
-                                      // bit 3 / 4: src uint8 / int16 (converting copies)
+                                      // bit 3 / 4: src uint8 / int16 (converting copies); bit 5: no source
+                                      // (multi_accumulate only)
 };
 void multi_copy(const CopyArgs& a, hipStream_t s);
+// gradient accumulation over the same tables: dst[t] (fp32) = (dst[t] + src[t]) * scale, an add and a multiply (two
+// roundings, never fused); src fp32 (dts bit 0), bf16, or none (dts bit 5, src unused: dst[t] *= scale); n in
+// elements, chunks of kCopyChunk; no raw-byte form
+void multi_accumulate(const CopyArgs& a, float scale, hipStream_t s);
 
 // Column-block assembly over a shared row count (fp32): output piece p is rows x width[p] columns of dst[p] (row
 // pitch dld[p], first column doff[p]) = the sum of nsrc[p] (1..3) column blocks of the sources (pitch sld, first
@@ -450,6 +455,8 @@ struct StridedCopyArgs {                 // passed by value (~2.1 KB of kernel a
   unsigned char dts[kSCopyMaxT];         // bit 0: src fp32, bit 1: dst fp32 (else bf16), bit 2: tiled transpose
 };
 void multi_strided_copy(const StridedCopyArgs& a, hipStream_t s);
+// dst[t][i] (fp32) = (dst[t][i] + the source element the copy would read) * scale, both forms of the copy
+void multi_strided_accumulate(const StridedCopyArgs& a, float scale, hipStream_t s);
 
 // ---- pointwise.hip -----------------------------------------------------------------------------
 // y [P, cout] bf16 = act(x [P, cin] bf16 . w^T (fp32 [cout, cin]) + bias); cin, cout in {8, 16, 32}

@@ -5,7 +5,9 @@
 * builds the trainer (model + optimizer + bucketed gradient reducer + clip), dataloader, hooks;
 * ``run()``: ``before_run`` hooks, then ``max_iterations`` x (data -> ``before_iter`` -> trainer step ->
   ``after_iter``), then ``after_run``; wrapped in :func:`auto_checkpoint` so an exception or
-  SIGINT/SIGTERM/SIGUSR1 saves a checkpoint first (``base_learner.py:248-272``).
+  SIGINT/SIGTERM/SIGUSR1 saves a checkpoint first (``base_learner.py:248-272``).  With
+  ``learner.accumulate_steps`` = k > 1 an iteration is k batches (``micro_step`` on the first k - 1, the step on the
+  last) and one optimizer update.
 Subclasses override ``_setup_trainer`` / ``_setup_dataloader`` and may add hooks.
 """
 from __future__ import annotations
@@ -28,7 +30,7 @@ DEFAULT_BASE_LEARNER_CONFIG = {
     'learner': {'load_path': '', 'use_cuda': True, 'use_distributed': False, 'max_iterations': int(1e8),
                 'learning_rate': 1e-3, 'weight_decay': 1e-4, 'data': {'batch_size': 1, 'trajectory_length': 64},
                 'grad_clip': {'type': 'none', 'threshold': 1.4}, 'hook': DEFAULT_HOOK_CONFIG,
-                'player_id': 'MP0', 'log_to_stdout': True},
+                'player_id': 'MP0', 'log_to_stdout': True, 'accumulate_steps': 1},
 }
 
 
@@ -64,7 +66,11 @@ class BaseLearner:
         self.dataloader: Optional[Iterator] = self._setup_dataloader()
         self.hooks = build_learner_hooks(lc.hook)
         self._max_iterations = int(lc.max_iterations)
-        self.samples_per_iter = int(lc.data.batch_size) * int(lc.data.trajectory_length)
+        # gradient accumulation: an iteration (= one optimizer update) draws this many batches
+        self.accumulate_steps = int(lc.get('accumulate_steps', 1))
+        if self.accumulate_steps < 1:
+            raise ValueError('learner.accumulate_steps must be >= 1')
+        self.samples_per_iter = int(lc.data.batch_size) * int(lc.data.trajectory_length) * self.accumulate_steps
 
     # ------------------------------------------------------------------ overridables
     def _setup_trainer(self):
@@ -75,6 +81,10 @@ class BaseLearner:
 
     def _train(self, data: Dict) -> Dict:
         return self.trainer.step(data)
+
+    def _micro_train(self, data: Dict) -> Dict:
+        """A batch of an accumulation window that is not its last (``learner.accumulate_steps`` > 1)."""
+        return self.trainer.micro_step(data)
 
     # ------------------------------------------------------------------ properties used by hooks
     @property
@@ -132,11 +142,21 @@ class BaseLearner:
             data = self._next_data()
             t1 = time.time()
             self.call_hooks('before_iter')
+            # an accumulation window: k batches, one update; hooks, last_iter and checkpoints count updates.  The
+            # logged info is the last micro-batch's (no extra device -> host reads to average the others)
+            t_data = t1 - t0
+            for _ in range(self.accumulate_steps - 1):
+                self._micro_train(data)
+                t2 = time.time()
+                data = self._next_data()
+                t_data += time.time() - t2
             info = self._train(data)
+            if self.accumulate_steps > 1:
+                info['accumulated'] = self.accumulate_steps
             self.last_iter.add(1)
             self._log_info(info)
-            self.log_buffer['data_time'] = t1 - t0
-            self.log_buffer['train_time'] = time.time() - t1
+            self.log_buffer['data_time'] = t_data
+            self.log_buffer['train_time'] = time.time() - t0 - t_data
             self.call_hooks('after_iter')
             faults.inject('learner_iter')
         self.call_hooks('after_run')

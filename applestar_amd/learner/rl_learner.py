@@ -199,6 +199,10 @@ class RLLearner(BaseLearner):
                                    fraction=float(d.get('ring_fraction', 0.75)))
         return int(float(gb) * (1 << 30))
 
+    def _micro_train(self, data: Dict) -> Dict:
+        data.pop('model_last_iter', None)      # staleness is the window's last micro-batch's (_train)
+        return self.trainer.micro_step(data)
+
     def _train(self, data: Dict) -> Dict:
         mli = data.pop('model_last_iter', None)
         info = self.trainer.step(data)

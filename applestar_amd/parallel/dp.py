@@ -64,6 +64,46 @@ def copy_into(dst: List[torch.Tensor], src: List[torch.Tensor]):
         torch._foreach_copy_(dst, src)
 
 
+def accumulate_into(dst: List[torch.Tensor], src: List[Optional[torch.Tensor]], scale: float = 1.0):
+    """dst[i] = (dst[i] + src[i]) * scale for all i, in fp32 (gradient accumulation over micro-batches): the add and
+    the multiply are two roundings, a bf16 source is widened exactly.  A source of None adds nothing: its slot only
+    takes the scale.  ``dst`` must be fp32 - a partial sum is never kept in bf16.  One native multi-tensor launch on
+    the GPU (a second, strided one for the pairs ``copy_into`` sends there); ``torch._foreach_add_`` +
+    ``_foreach_mul_`` on the CPU."""
+    scale = float(scale)
+    if scale == 1.0:      # nothing to do for the slots without a source
+        keep = [i for i, s in enumerate(src) if s is not None]
+        dst, src = [dst[i] for i in keep], [src[i] for i in keep]
+    if not dst:
+        return
+    for d in dst:
+        if d.dtype != torch.float32:
+            raise TypeError(f'accumulate_into: fp32 accumulators only, got {d.dtype}')
+    if dst[0].is_cuda:
+        from ..ops import native
+        C = native.ensure_loaded()
+        same, sd, ss, spec = ([], []), [], [], []
+        for d, s in zip(dst, src):
+            if s is not None and d.stride() != s.stride() and d.is_contiguous() and 0 < s.dim() <= 4 and \
+                    s.numel() > 0 and s.dtype in (torch.float32, torch.bfloat16) and min(s.stride()) >= 0:
+                sd.append(d)
+                ss.append(s)
+                spec += native._view_spec(s, s)
+            else:
+                same[0].append(d)
+                same[1].append(s)
+        if same[0]:
+            C.multi_accumulate(same[0], same[1], scale)
+        if sd:
+            C.multi_strided_accumulate(sd, ss, spec, scale)
+    else:
+        pairs = [(d, s) for d, s in zip(dst, src) if s is not None]
+        if pairs:
+            torch._foreach_add_([d for d, _ in pairs], [s if s.dtype == torch.float32 else s.float() for _, s in pairs])
+        if scale != 1.0:
+            torch._foreach_mul_(dst, scale)
+
+
 class _Bucket:
     __slots__ = ('params', 'flat', 'ready', 'handle', 'comm')
 
@@ -152,18 +192,27 @@ class GradientReducer:
         op = dist.ReduceOp.AVG if self.use_avg else dist.ReduceOp.SUM
         b.handle = dist.all_reduce(buf, op=op, group=self.group, async_op=True)
 
-    def backward(self, loss: torch.Tensor, before_copy=None):
+    def backward(self, loss: torch.Tensor, before_copy=None, accumulate: bool = False, scale: float = 1.0,
+                 no_collective: bool = False):
         """Gradients of ``loss`` into the bucket views: ``autograd.grad`` + one multi-tensor copy (native on
         the GPU), at every world size; buckets holding a parameter without a gradient are zeroed first.
-        ``before_copy``: called between autograd and the copy (the deferred weight gradients join there)."""
+        ``before_copy``: called between autograd and the copy (the deferred weight gradients join there).
+        ``accumulate``: micro-batch 2..k of an accumulation window - the copy becomes ``(bucket + g) * scale``
+        (:func:`accumulate_into`; ``scale`` is 1 until the window's last micro-batch, then 1/k) and nothing is
+        zeroed.  ``no_collective`` (every micro-batch but the last) only matters to ``backward_phased``."""
         grads = torch.autograd.grad(loss, self.params, allow_unused=True)
         if before_copy is not None:
             before_copy()
-        self._store(self.params, grads, self.buckets)
+        self._store(self.params, grads, self.buckets, accumulate, scale)
 
-    def _store(self, params, grads, buckets):
+    def _store(self, params, grads, buckets, accumulate: bool = False, scale: float = 1.0):
         if self.grad_hook is not None:
             self.grad_hook(params, grads)
+        if accumulate:
+            # a parameter without a gradient in this micro-batch adds nothing (its slot keeps the earlier sum, nothing
+            # is zeroed); the window's closing scale still reaches every slot, in the same launch
+            accumulate_into([p.grad for p in params], list(grads), scale)
+            return
         dst, src = [], []
         stale = set()
         for p, g in zip(params, grads):
@@ -177,26 +226,30 @@ class GradientReducer:
                 b.flat.zero_()
         copy_into(dst, src)
 
-    def backward_phased(self, loss: torch.Tensor, boundary, before_copy=None):
+    def backward_phased(self, loss: torch.Tensor, boundary, before_copy=None, accumulate: bool = False,
+                        scale: float = 1.0, no_collective: bool = False):
         """Two-phase backward (module docstring): phase 1 = the loss w.r.t. the phase-0 parameters and the
         boundary leaves; their buckets are filled and (multi-rank) their all-reduce issued; phase 2 = the encoder
         outputs, with the leaves' gradients, w.r.t. the phase-1 parameters.  ``boundary``: the (encoder output,
-        leaf) pairs of ``Model.encoder_boundary``.  ``before_copy`` runs before the first copy."""
+        leaf) pairs of ``Model.encoder_boundary``.  ``before_copy`` runs before the first copy.  ``accumulate`` /
+        ``scale``: as in :meth:`backward`; ``no_collective``: the early all-reduce is not issued (the buckets
+        hold a partial sum until the window's last micro-batch)."""
         p0, p1 = self.phase_params
         outs, leaves = [o for o, _ in boundary], [lf for _, lf in boundary]
         g = torch.autograd.grad(loss, p0 + leaves, allow_unused=True)
         if before_copy is not None:
             before_copy()
-        self._store(p0, g[:len(p0)], self.phase_buckets[0])
-        for b in self.phase_buckets[0]:
-            self._launch(b)               # RCCL's stream, beside the encoders' backward below
+        self._store(p0, g[:len(p0)], self.phase_buckets[0], accumulate, scale)
+        if not no_collective:
+            for b in self.phase_buckets[0]:
+                self._launch(b)               # RCCL's stream, beside the encoders' backward below
         roots = [(t, gt) for t, gt in zip(outs, g[len(p0):]) if gt is not None]
         if roots and p1:
             g2 = torch.autograd.grad([t for t, _ in roots], p1, grad_outputs=[gt for _, gt in roots],
                                      allow_unused=True)
         else:
             g2 = [None] * len(p1)
-        self._store(p1, g2, self.phase_buckets[1])
+        self._store(p1, g2, self.phase_buckets[1], accumulate, scale)
 
     def zero_grad(self, buffers: bool = True):
         """Reset the per-step state; ``buffers=False`` leaves the bucket memory alone (``backward`` overwrites

@@ -17,7 +17,7 @@ from typing import Dict, List
 import torch
 import torch.nn as nn
 
-from .dp import GradientReducer, copy_into
+from .dp import GradientReducer, accumulate_into, copy_into
 
 LOWP_MODULES = (nn.Linear, nn.Conv2d, nn.ConvTranspose2d)
 
@@ -92,22 +92,32 @@ class MasterWeights:
     def zero_grad(self):
         self.reducer.zero_grad()
 
-    def backward(self, loss: torch.Tensor, boundary=None):
+    def backward(self, loss: torch.Tensor, boundary=None, accumulate: bool = False, scale: float = 1.0,
+                 no_collective: bool = False):
         """Backward straight into the fp32 master gradient, with the same launches at every world size:
         ``autograd.grad`` (no per-parameter ``AccumulateGrad`` add into zeroed buckets) and ONE native
         multi-tensor copy that writes every bf16 gradient, converted, into its fp32 master-grad slot (and the
         fp32 ones into their buckets).  Multi-rank, :meth:`synchronize` then all-reduces the flat fp32
         buffers (fp32 reduction of the bf16 gradients; parallel/dp.py explains why the collective is not
-        overlapped with backward through per-parameter hooks)."""
+        overlapped with backward through per-parameter hooks).
+
+        ``accumulate`` (micro-batch 2..k of an accumulation window): the copy becomes ``(slot + g) * scale`` in
+        the fp32 master gradient / fp32 buckets (parallel/dp.py ``accumulate_into``), nothing is zeroed;
+        ``no_collective`` (every micro-batch but the last): the phase-0 all-reduce is not issued early."""
         self._direct = False
         self._pending = []
         self._phase0_issued = False
         if not loss.is_cuda:
+            if accumulate:
+                # this path stores bf16 gradients in the bf16 buckets and widens them in synchronize(): a window
+                # would have to sum there, in bf16
+                raise RuntimeError('gradient accumulation with master weights needs the GPU path: the CPU path '
+                                   'keeps gradients in bf16 buckets and a partial sum is never kept in bf16')
             self.reducer.backward(loss)
             return
         if boundary is None:
             grads = torch.autograd.grad(loss, self.reducer.params, allow_unused=True)
-            self._store(self.reducer.params, grads, None)
+            self._store(self.reducer.params, grads, None, accumulate, scale)
             self._direct = True
             return
         # two phases (parallel/dp.py backward_phased): the phase-0 master range and fp32 buckets are final after
@@ -115,19 +125,24 @@ class MasterWeights:
         p0, p1 = self.reducer.phase_params
         outs, leaves = [o for o, _ in boundary], [lf for _, lf in boundary]
         g = torch.autograd.grad(loss, p0 + leaves, allow_unused=True)
-        self._store(p0, g[:len(p0)], 0)
+        self._store(p0, g[:len(p0)], 0, accumulate, scale)
         self._direct = True
-        self._issue(0)
-        self._phase0_issued = True
+        if not no_collective:
+            self._issue(0)
+            self._phase0_issued = True
         roots = [(t, gt) for t, gt in zip(outs, g[len(p0):]) if gt is not None]
         g2 = torch.autograd.grad([t for t, _ in roots], p1, grad_outputs=[gt for _, gt in roots],
                                  allow_unused=True) if roots and p1 else [None] * len(p1)
-        self._store(p1, g2, 1)
+        self._store(p1, g2, 1, accumulate, scale)
 
-    def _store(self, params, grads, phase):
+    def _store(self, params, grads, phase, accumulate: bool = False, scale: float = 1.0):
         """Every gradient, converted, into its fp32 master-grad slot (fp32 ones into their buckets); ``phase``:
-        which master range / fp32 buckets these parameters own (None: all)."""
+        which master range / fp32 buckets these parameters own (None: all).  ``accumulate``: added to the slot and
+        the sum scaled instead (GradientReducer._store)."""
         mg = self._master_grad_views()
+        if accumulate:     # a slot without a gradient this time adds nothing and takes the scale all the same
+            accumulate_into([mg.get(p, p.grad) for p in params], list(grads), scale)
+            return
         dst, src = [], []
         for p, g in zip(params, grads):
             if g is not None:

@@ -36,6 +36,9 @@ DEFAULT_LEARNER_CONFIG = AttrDict({
         # ordered kernels at every summation site that has one (ops.set_deterministic; docs/OPEN_ISSUES.md
         # 'Determinism'); can only turn the mode on, APPLESTAR_DETERMINISTIC=1 is never overridden
         'deterministic': False,
+        # gradient accumulation: micro-batches per optimizer update (the learner loop draws this many batches per
+        # iteration; micro_step on all but the last).  Not available with graph_step
+        'accumulate_steps': 1,
     },
     'model': {'enable_baselines': ['winloss']},
 })
@@ -63,19 +66,29 @@ class RLTrainer(TrainEngine):
             self.remain_value_pretrain -= 1
 
     # ------------------------------------------------------------------ one iteration, in three parts
-    def _fwd_bwd(self, batch: Dict) -> Dict[str, torch.Tensor]:
+    def _fwd_bwd(self, batch: Dict, more: bool = False) -> Dict[str, torch.Tensor]:
         if not self.model.training:   # train() walks ~670 modules: ~1 ms of host time per step
             self.model.train()
         with amp_context(self.device, self.amp_dtype):
             out = self.model.rl_learner_forward(**batch)
         info = self.loss.compute_loss(out)
-        self.backward(info['total_loss'])
+        self.backward(info['total_loss'], more=more)
         # detached: a returned loss must not keep this step's autograd graph (and its AccumulateGrad nodes,
         # bound to the stream they were created on) alive into the next step - or into a graph capture
         return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in info.items()}
 
+    def micro_step(self, batch: Dict) -> Dict[str, torch.Tensor]:
+        """One micro-batch of a gradient-accumulation window that is not its last: forward, loss, and the gradient
+        added to the window (``backward(more=True)``: no collective, no update).  :meth:`step` on the window's last
+        batch closes it; the optimizer then sees the mean of the micro-batch gradients, and ``iter`` counts that
+        update only.  Returns this micro-batch's detached info."""
+        if self._window == 0:
+            self._value_pretrain_toggle()     # once per window, before its first micro-batch
+        return self._fwd_bwd(batch, more=True)
+
     def step(self, batch: Dict) -> Dict[str, torch.Tensor]:
-        self._value_pretrain_toggle()
+        if self._window == 0:
+            self._value_pretrain_toggle()
         if self.graph is not None and 'entity_total' in batch:
             from ..models.encoders import entity_pad_for
             b = dict(batch)

@@ -51,7 +51,8 @@ class TrainEngine:
     """Base of :class:`~applestar_amd.rl.trainer.RLTrainer` / :class:`~applestar_amd.sl.trainer.SLTrainer`.
 
     Subclasses set ``self.cfg`` (with a ``learner`` section), build ``self.model`` and call
-    :meth:`_setup_engine`; a step is then ``backward(loss)`` -> ``_reduce()`` -> ``_update()``."""
+    :meth:`_setup_engine`; a step is then ``backward(loss)`` -> ``_reduce()`` -> ``_update()``; with gradient
+    accumulation, ``backward(loss, more=True)`` for the window's first k - 1 micro-batches comes before it."""
 
     # optimizer hyper-parameters of the learner (the reference's RL learner: betas (0, 0.99), eps 1e-5)
     ADAM_BETAS = (0.9, 0.999)
@@ -106,6 +107,15 @@ class TrainEngine:
         # the step's health gate lives in ONE device scalar: a captured update graph reads it by address
         self._gate = torch.ones((), dtype=torch.float32, device=self.device) if self.device.type == 'cuda' else None
         self.graph = None
+        # gradient accumulation (backward(more=True)): micro-batches summed into the flat gradient buffers so far;
+        # 0 = no window open.  The partial sum lives only in those buffers, never in a state_dict
+        self._window = 0
+        self.accumulate_steps = int(lc.get('accumulate_steps', 1))
+        if self.accumulate_steps < 1:
+            raise ValueError('learner.accumulate_steps must be >= 1')
+        if self.accumulate_steps > 1 and bool(lc.get('graph_step', False)):   # on any device: a config error
+            raise ValueError('learner.accumulate_steps > 1 is not supported together with graph_step '
+                             '(accumulation inside a captured step is not implemented)')
         self.reset_optimizer()
 
     # ------------------------------------------------------------------ optimizer
@@ -113,8 +123,9 @@ class TrainEngine:
         return self.device.type == 'cuda' and bool(self.cfg.learner.get('graph_step', False))
 
     def reset_optimizer(self):
-        """Fresh optimizer state (also used after a league reset)."""
+        """Fresh optimizer state (also used after a league reset); an open accumulation window is discarded."""
         lc = self.cfg.learner
+        self._window = 0
         self.optimizer = build_optimizer(self.opt_params, lc, betas=self.ADAM_BETAS, eps=self.ADAM_EPS,
                                          device=self.device)
         self.lr_scheduler = None            # the RL learner's LR is constant (rl_learner.py: MultiStepLR, no milestones)
@@ -161,7 +172,24 @@ class TrainEngine:
             return forced == '1'
         return pdist.get_world_size() > 1 and bool(self.cfg.learner.get('overlap_backward', True))
 
-    def backward(self, loss: torch.Tensor):
+    def backward(self, loss: torch.Tensor, more: bool = False):
+        """Gradient of ``loss`` into the flat buffers.  ``more=True``: this is one micro-batch of an accumulation
+        window and more follow - its gradient is added to the open window (one is opened if none is), and no
+        collective is launched.  ``more=False`` with a window of k - 1 micro-batches open: added as the k-th, the
+        sum scaled by 1/k (the optimizer sees the mean of the k gradients) and the window closed; with no window
+        open it is the plain one-batch backward.  Each micro-batch keeps its own deferred-dW bracket and
+        encoder boundary; ``_reduce`` / ``_update`` follow the closing call only."""
+        done = self._window      # micro-batches already in the open window
+        if (more or done) and bool(self.cfg.learner.get('graph_step', False)):
+            raise ValueError('gradient accumulation (backward(more=True) / accumulate_steps > 1) is not supported '
+                             'together with graph_step')
+        self._window = done + 1 if more else 0
+        if not more and not done:
+            self._backward(loss)
+        else:
+            self._backward(loss, accumulate=done > 0, scale=1.0 if more else 1.0 / (done + 1), no_collective=more)
+
+    def _backward(self, loss: torch.Tensor, **kw):
         self.reducer.zero_grad(buffers=False)    # backward overwrites every slot (and zeroes unused ones)
         from ..ops import native
         boundary = getattr(self.model, 'encoder_boundary', None)
@@ -173,11 +201,11 @@ class TrainEngine:
         try:
             join = (lambda: native.defer_end(self.device)) if defer else None
             if self.master is not None:
-                self.master.backward(loss, boundary if phased else None)
+                self.master.backward(loss, boundary if phased else None, **kw)
             elif phased:
-                self.reducer.backward_phased(loss, boundary, before_copy=join)
+                self.reducer.backward_phased(loss, boundary, before_copy=join, **kw)
             else:
-                self.reducer.backward(loss, before_copy=join)
+                self.reducer.backward(loss, before_copy=join, **kw)
         finally:
             if defer:
                 native.defer_end(self.device)
@@ -250,6 +278,7 @@ class TrainEngine:
 
     def on_model_changed(self):
         """Call after editing model weights in place (e.g. a value-network reset)."""
+        self._window = 0      # a partial gradient sum of the old weights is of no use
         if self.master is not None:
             self.master.sync_from_model()
         elif self.derived is not None:
@@ -260,6 +289,7 @@ class TrainEngine:
                 'last_iter': self.iter, 'grad_clip': self.grad_clip.state_dict()}
 
     def load_state_dict(self, sd, load_optimizer=True):
+        self._window = 0
         self.load_model_state_dict(sd['model'])
         if load_optimizer and 'optimizer' in sd:
             self.optimizer.load_state_dict(sd['optimizer'])

@@ -27,6 +27,7 @@ DEFAULT_SL_CONFIG = AttrDict({
         'bucket_mb': 32, 'comm_dtype': None,
         'amp_dtype': None,        # fp32 like the reference; 'bfloat16' = bf16 compute with fp32 masters
         'deterministic': False,   # ordered kernels where they exist (ops.set_deterministic); only ever turns the mode on
+        'accumulate_steps': 1,    # gradient accumulation: chunks per optimizer update (micro_step on all but the last)
     },
 })
 
@@ -50,7 +51,17 @@ class SLTrainer(TrainEngine):
         self.hidden_state = [(torch.where(mask[:, None], 0.0, h.detach()), torch.where(mask[:, None], 0.0, c.detach()))
                              for h, c in self.hidden_state]
 
+    def micro_step(self, batch: Dict) -> Dict[str, torch.Tensor]:
+        """One chunk of a gradient-accumulation window that is not its last: as :meth:`step` (the carried hidden
+        state handled per call: consecutive micro-batches are consecutive chunks of the same slots), but the
+        gradient is only added to the window - no collective, no update, no scheduler step.  During the warm-up
+        (``ignore_steps`` counts calls) nothing is accumulated, so a window only opens once it is over."""
+        return self._chunk(batch, more=True)
+
     def step(self, batch: Dict) -> Dict[str, torch.Tensor]:
+        return self._chunk(batch, more=False)
+
+    def _chunk(self, batch: Dict, more: bool) -> Dict[str, torch.Tensor]:
         if not self.model.training:   # train() walks ~670 modules: ~1 ms of host time per step
             self.model.train()
         batch = dict(batch)
@@ -61,11 +72,14 @@ class SLTrainer(TrainEngine):
         info = self.loss.compute_loss(logits, batch['action_info'], batch['action_mask'], batch['selected_units_num'],
                                       batch['entity_num'], infer_action)
         if self.iter >= self.ignore_steps:
-            self.backward(info['total_loss'])
-            self._reduce()
-            info['gradient'] = self._update()
-            self.lr_scheduler.step()
-            self.step_info(info)
+            self.backward(info['total_loss'], more=more)
+            if not more:
+                self._reduce()
+                info['gradient'] = self._update()
+                self.lr_scheduler.step()
+                self.step_info(info)
         self.hidden_state = [(h.detach(), c.detach()) for h, c in hidden]
         self.iter += 1
+        if more:    # nothing of a micro-batch's autograd graph outlives the call
+            info = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in info.items()}
         return info
