@@ -16,11 +16,12 @@
 #include "../kernels.h"
 #include "../split_mfma.h"
 #include "../f32_pipe.h"
+#include "../wgrad_tile.h"
 
 namespace as {
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f16v;
+using pipe::f16v;
 
 template <int BN_, int BK_>
 struct WgF32Cfg {
@@ -43,13 +44,9 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const float* __restrict_
   using C = WgF32Cfg<BN, BK>;
   __shared__ __attribute__((aligned(16))) float smem[2 * C::STAGE];
 
-  const int wg = xcd_remap();
-  const int tk = wg % tiles_k;
-  const int tn = (wg / tiles_k) % tiles_n;
-  const int s = wg / (tiles_k * tiles_n);
-  const int n0 = tn * BN, k0 = tk * BK;
-  const long r_begin = static_cast<long>(s) * rows_per_split;
-  const long r_end = r_begin + rows_per_split < R ? r_begin + rows_per_split : R;
+  const WgTile T = wg_tile<BN, BK>(xcd_remap(), tiles_n, tiles_k, rows_per_split, R);
+  const int tk = T.tk, s = T.s, n0 = T.n0, k0 = T.k0;
+  const long r_begin = T.r_begin, r_end = T.r_end;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wn = wid / C::WK, wk = wid % C::WK;
@@ -64,27 +61,17 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const float* __restrict_
   // per-thread piece columns (fixed across stages): CHA and CHB divide NT
   const int a_col = n0 + 4 * (tid % C::CHA);
   const int b_col = k0 + 4 * (tid % C::CHB);
-  int b_c = b_col, b_dy = 0, b_dx = 0;
-  if (CONV) {
-    const int tap = b_col / Cin;
-    b_c = b_col - tap * Cin;
-    b_dy = tap / 3 - 1;
-    b_dx = tap % 3 - 1;
-  }
+  WgConvPiece<CONV> xp;
+  xp.init(b_col, Cin);
   const bool a_ok = a_col < N, b_ok = b_col < K;
   // conv pieces: image coordinates of each piece's row, advanced by BR rows per stage (32-bit offsets: the
   // host keeps every operand below 2^31 bytes).  Replaces a 64-bit modulo and two divisions per piece and
   // stage, which were the bulk of the loop's VALU work on the narrow (Cout 32 / 64) tiles.
-  int py[C::B_IT], px[C::B_IT];
-  const int adv_y = C::BR / W, adv_x = C::BR % W;
+  ImageCursor cur[C::B_IT];
+  const ImageCursor adv = ImageCursor::stride(C::BR, W);
   if (CONV) {
 #pragma unroll
-    for (int i = 0; i < C::B_IT; ++i) {
-      const long r = r_begin + (tid + i * C::NT) / C::CHB;
-      const int rem = static_cast<int>(r % HW);
-      py[i] = rem / W;
-      px[i] = rem - py[i] * W;
-    }
+    for (int i = 0; i < C::B_IT; ++i) cur[i].init(r_begin + (tid + i * C::NT) / C::CHB, HW, W);
   }
 
   uint4 ra[C::A_IT], rb[C::B_IT];
@@ -101,13 +88,10 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const float* __restrict_
       const long r = rs + (tid + i * C::NT) / C::CHB;
       int off = kOOB;
       if (CONV) {
-        const int yy = py[i] + b_dy, xx = px[i] + b_dx;
-        if (b_ok && r < r_end && yy >= 0 && yy < H && xx >= 0 && xx < W)
-          off = ((static_cast<int>(r) + b_dy * W + b_dx) * Cin + b_c) * 4;
-        px[i] += adv_x;
-        py[i] += adv_y;
-        if (px[i] >= W) { px[i] -= W; ++py[i]; }
-        while (py[i] >= H) py[i] -= H;
+        // the tap test is spelled out here: as a bool helper it moved two kernels' register allocation
+        const int yy = cur[i].y + xp.dy, xx = cur[i].x + xp.dx;
+        if (b_ok && r < r_end && yy >= 0 && yy < H && xx >= 0 && xx < W) off = xp.offset(static_cast<int>(r), W, Cin);
+        cur[i].advance(adv, H, W);
       } else if (b_ok && r < r_end) {
         off = (static_cast<int>(r) * K + b_col) * 4;
       }
@@ -205,7 +189,8 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const float* __restrict_
   }
 
   // accumulator (i, j) register e: n = n0 + wn TN + 32 i + (e&3) + 8 (e>>2) + 4 h, k = k0 + wk TK + 32 j + l32:
-  // 32 lanes store 128 contiguous bytes of one dW row
+  // 32 lanes store 128 contiguous bytes of one dW row.  This store and the db reduction below are spelled out in each
+  // kernel: as shared helpers they moved the ring and split-once kernels' register allocation
   float* outp = dw_part + static_cast<long>(s) * part_stride;
 #pragma unroll
   for (int i = 0; i < C::FN; ++i)
@@ -235,63 +220,49 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const float* __restrict_
 // read 32 consecutive floats of one row).  The conv form's X piece of a lane is a fixed 4-channel group of one tap
 // (the lane's column is the same in every stage); its row's image coordinates advance by 16 rows per issued step.
 template <int BN, int BK, bool CONV, int NS>
-__global__ __launch_bounds__(256, ((BN == 128 && BK >= 128) || BN == 32) ? 2 : 3) void wgrad_f32_pipe_kernel(const float* __restrict__ dy,
+__global__ __launch_bounds__(256, (BN == 128 && BK >= 128) ? 2 : 3) void wgrad_f32_pipe_kernel(const float* __restrict__ dy,
                                                                 const float* __restrict__ x,
                                                                 float* __restrict__ dw_part, float* __restrict__ db_part,
                                                                 long part_stride, long R, int N, int K, int H, int W,
                                                                 int Cin, long rows_per_split, int tiles_n, int tiles_k) {
-  // a 32-wide N tile takes 32 reduction rows per stage (two MFMA K-steps) so its dY rows still fill one 4-KB
-  // DMA wave-instruction per wave
-  constexpr int RS = BN == 32 ? 32 : 16, SUB = RS / 16;
+  constexpr int RS = 16;
   constexpr int A_BYTES = RS * BN * 4, B_BYTES = RS * BK * 4, STAGE = A_BYTES + B_BYTES;
   constexpr int A_PW = A_BYTES / 4096, B_PW = B_BYTES / 4096;          // DMA wave-instructions per wave
   constexpr int A_CPR = BN / 4, B_CPR = BK / 4;                       // 16-B pieces per row
   constexpr int A_RPI = 64 / A_CPR, B_RPI = 64 / B_CPR;               // rows per wave-instruction
   static_assert(A_PW >= 1 && B_PW >= 1 && A_PW * 4096 == A_BYTES && B_PW * 4096 == B_BYTES, "tile / DMA mismatch");
-  constexpr int WN = BN >= 64 ? 2 : 1, WK = 4 / WN;
+  constexpr int WN = 2, WK = 2;
   constexpr int TN = BN / WN, TK = BK / WK, FN = TN / 32, FK = TK / 32;
-  static_assert(NS == 3, "three stage arrays");
+  static_assert(NS == 3 && BN >= 64, "three stage arrays; 2 x 2 waves");
   __shared__ __attribute__((aligned(16))) char s0[STAGE], s1[STAGE], s2[STAGE];
   char* const smem[3] = {s0, s1, s2};
 
-  const int wg = pipe::xcd_remap();
-  const int tk = wg % tiles_k;
-  const int tn = (wg / tiles_k) % tiles_n;
-  const int s = wg / (tiles_k * tiles_n);
-  const int n0 = tn * BN, k0 = tk * BK;
-  const long r_begin = static_cast<long>(s) * rows_per_split;
-  const long r_end = r_begin + rows_per_split < R ? r_begin + rows_per_split : R;
+  const WgTile T = wg_tile<BN, BK>(pipe::xcd_remap(), tiles_n, tiles_k, rows_per_split, R);
+  const int tk = T.tk, s = T.s, n0 = T.n0, k0 = T.k0;
+  const long r_begin = T.r_begin, r_end = T.r_end;
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wid / WK, wk = wid % WK;
   const int l32 = lane & 31, h = lane >> 5;
   const long HW = static_cast<long>(H) * W;
   const pipe::i32x4 yr = pipe::rsrc(dy, R * N * 4), xr = pipe::rsrc(x, CONV ? R * Cin * 4 : R * K * 4);
 
-  // DMA pieces: fixed column per lane, row (within a step) per chunk
+  // DMA pieces: fixed column per lane, row (within a step) per chunk.  Spelled out here and in the split-once kernel:
+  // as one shared struct the setup and the issue moved both kernels' register allocation
   const int a_col = n0 + 4 * (lane % A_CPR), b_col = k0 + 4 * (lane % B_CPR);
   int a_row[A_PW], b_row[B_PW];
 #pragma unroll
   for (int c = 0; c < A_PW; ++c) a_row[c] = (wid + 4 * c) * A_RPI + lane / A_CPR;
 #pragma unroll
   for (int c = 0; c < B_PW; ++c) b_row[c] = (wid + 4 * c) * B_RPI + lane / B_CPR;
-  int b_c = b_col, b_dy = 0, b_dx = 0;
-  if (CONV) {
-    const int tap = b_col / Cin;
-    b_c = b_col - tap * Cin;
-    b_dy = tap / 3 - 1;
-    b_dx = tap % 3 - 1;
-  }
+  WgConvPiece<CONV> xp;
+  xp.init(b_col, Cin);
   const bool a_ok = a_col < N, b_ok = b_col < K;
   // conv: image coordinates of each chunk's row for the next step to issue (advanced by RS rows per issue)
-  int py[B_PW], px[B_PW];
-  const int adv_y = RS / W, adv_x = RS % W;
+  ImageCursor cur[B_PW];
+  const ImageCursor adv = ImageCursor::stride(RS, W);
   if (CONV) {
 #pragma unroll
-    for (int c = 0; c < B_PW; ++c) {
-      const int rem = static_cast<int>((r_begin + b_row[c]) % HW);
-      py[c] = rem / W;
-      px[c] = rem - py[c] * W;
-    }
+    for (int c = 0; c < B_PW; ++c) cur[c].init(r_begin + b_row[c], HW, W);
   }
   const long nsteps = r_end > r_begin ? (r_end - r_begin + RS - 1) / RS : 0;
   auto issue = [&](char* st, long kt) {
@@ -307,13 +278,11 @@ __global__ __launch_bounds__(256, ((BN == 128 && BK >= 128) || BN == 32) ? 2 : 3
       const long r = r0 + b_row[c];
       int off = pipe::kOOB;
       if (CONV) {
-        const int yy = py[c] + b_dy, xx = px[c] + b_dx;
+        // the tap test is spelled out here: as a bool helper it moved two kernels' register allocation
+        const int yy = cur[c].y + xp.dy, xx = cur[c].x + xp.dx;
         if (kt < nsteps && b_ok && r < r_end && yy >= 0 && yy < H && xx >= 0 && xx < W)
-          off = ((static_cast<int>(r) + b_dy * W + b_dx) * Cin + b_c) * 4;
-        px[c] += adv_x;
-        py[c] += adv_y;
-        if (px[c] >= W) { px[c] -= W; ++py[c]; }
-        while (py[c] >= H) py[c] -= H;
+          off = xp.offset(static_cast<int>(r), W, Cin);
+        cur[c].advance(adv, H, W);
       } else if (kt < nsteps && b_ok && r < r_end) {
         off = (static_cast<int>(r) * K + b_col) * 4;
       }
@@ -338,50 +307,47 @@ __global__ __launch_bounds__(256, ((BN == 128 && BK >= 128) || BN == 32) ? 2 : 3
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     issue(next, kt + NS - 1);
+    const float* A = reinterpret_cast<const float*>(st) + 8 * h * BN + wn * TN + l32;
+    const float* Bt = reinterpret_cast<const float*>(st + A_BYTES) + 8 * h * BK + wk * TK + l32;
+    float av[FN][8];
 #pragma unroll
-    for (int sub = 0; sub < SUB; ++sub) {
-      const float* A = reinterpret_cast<const float*>(st) + (16 * sub + 8 * h) * BN + wn * TN + l32;
-      const float* Bt = reinterpret_cast<const float*>(st + A_BYTES) + (16 * sub + 8 * h) * BK + wk * TK + l32;
-      float av[FN][8];
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+      for (int i = 0; i < FN; ++i) av[i][t] = A[t * BN + 32 * i];
+    Split3 sa[FN];
+#pragma unroll
+    for (int i = 0; i < FN; ++i) sa[i] = split8(av[i]);
+    if constexpr (FK <= 2) {
+      float bv[FK][8];
 #pragma unroll
       for (int t = 0; t < 8; ++t)
 #pragma unroll
-        for (int i = 0; i < FN; ++i) av[i][t] = A[t * BN + 32 * i];
-      Split3 sa[FN];
+        for (int j = 0; j < FK; ++j) bv[j][t] = Bt[t * BK + 32 * j];
+      Split3 sb[FK];
 #pragma unroll
-      for (int i = 0; i < FN; ++i) sa[i] = split8(av[i]);
-      if constexpr (FK <= 2) {
-        float bv[FK][8];
+      for (int j = 0; j < FK; ++j) sb[j] = split8(bv[j]);
 #pragma unroll
-        for (int t = 0; t < 8; ++t)
+      for (int i = 0; i < FN; ++i)
 #pragma unroll
-          for (int j = 0; j < FK; ++j) bv[j][t] = Bt[t * BK + 32 * j];
-        Split3 sb[FK];
+        for (int j = 0; j < FK; ++j) acc[i][j] = mfma_x6(sa[i], sb[j], acc[i][j]);
+    } else {
+      // the wide tile (64 x 128 per wave: 2 dY + 4 X fragments per 48 MFMAs, 25 % less split VALU per MFMA than
+      // 64 x 64): X fragments streamed one at a time
 #pragma unroll
-        for (int j = 0; j < FK; ++j) sb[j] = split8(bv[j]);
+      for (int j = 0; j < FK; ++j) {
+        float bv[8];
 #pragma unroll
-        for (int i = 0; i < FN; ++i)
+        for (int t = 0; t < 8; ++t) bv[t] = Bt[t * BK + 32 * j];
+        const Split3 sb = split8(bv);
 #pragma unroll
-          for (int j = 0; j < FK; ++j) acc[i][j] = mfma_x6(sa[i], sb[j], acc[i][j]);
-      } else {
-        // the wide tile (64 x 128 per wave: 2 dY + 4 X fragments per 48 MFMAs, 25 % less split VALU per MFMA than
-        // 64 x 64): X fragments streamed one at a time
-#pragma unroll
-        for (int j = 0; j < FK; ++j) {
-          float bv[8];
-#pragma unroll
-          for (int t = 0; t < 8; ++t) bv[t] = Bt[t * BK + 32 * j];
-          const Split3 sb = split8(bv);
-#pragma unroll
-          for (int i = 0; i < FN; ++i) acc[i][j] = mfma_x6(sa[i], sb, acc[i][j]);
-        }
+        for (int i = 0; i < FN; ++i) acc[i][j] = mfma_x6(sa[i], sb, acc[i][j]);
       }
-      if (do_bias) {
+    }
+    if (do_bias) {
 #pragma unroll
-        for (int i = 0; i < FN; ++i)
+      for (int i = 0; i < FN; ++i)
 #pragma unroll
-          for (int t = 0; t < 8; ++t) bsum[i] += av[i][t];
-      }
+        for (int t = 0; t < 8; ++t) bsum[i] += av[i][t];
     }
   };
   issue(smem[0], 0);
@@ -431,50 +397,37 @@ __global__ __launch_bounds__(256, ((BN == 128 && BK >= 128) || BN == 32) ? 2 : 3
 //            (thread t: column t % 128, rows 8 (t / 128) .. + 7, of dY and of X) beside MFMA(kt) on P(kt)
 // so the split of the next step and the products of this one share a barrier interval.  80 KB of LDS: 2
 // workgroups per CU.  db: each thread's dY column sums, the two row halves combined through LDS at the end.
-// Narrow N tiles (BN = 32 / 64: the 76x80 / 19x20 convs with 32 / 64 output channels, round 6): the same stages
-// with the four waves along K (each wave 32 (BN = 32) or 64 x 32 of the tile), the dY stage DMA'd by the first
-// A_N waves, and dY split by the first 2 BN threads; 50 / 60 KB of LDS (3 / 2 workgroups per CU).
-template <int BN>
 struct StgCfg {
-  static constexpr int BK = 128, RS = 16;
-  static constexpr int WN = BN == 128 ? 2 : 1, WK = 4 / WN;
+  static constexpr int BN = 128, BK = 128, RS = 16;
+  static constexpr int WN = 2, WK = 2;
   static constexpr int FN = BN / (32 * WN), FK = BK / (32 * WK);   // 32 x 32 blocks per wave along N / K
   static constexpr int A_BYTES = RS * BN * 4, B_BYTES = RS * BK * 4, FST = A_BYTES + B_BYTES;
-  static constexpr int A_N = A_BYTES / 1024, B_N = B_BYTES / 1024;  // 1 KB DMA wave-instructions per stage
-  static constexpr int A_PW = (A_N + 3) / 4, B_PW = B_N / 4;
+  static constexpr int A_PW = A_BYTES / 4096, B_PW = B_BYTES / 4096;
   static constexpr int A_CPR = BN / 4, B_CPR = BK / 4, A_RPI = 64 / A_CPR, B_RPI = 64 / B_CPR;
   static constexpr int PLA = (BN / 32) * 2 * 32 * 16, PLB = (BK / 32) * 2 * 32 * 16;   // one plane of dY / X
   static constexpr int PST = 3 * (PLA + PLB);
-  static constexpr int OCC = BN == 32 ? 3 : 2;
-  static_assert(B_N % 4 == 0 && (A_N % 4 == 0 || A_N < 4), "stage DMA split");
 };
 
-template <int BN, bool CONV>
-__global__ __launch_bounds__(256, StgCfg<BN>::OCC) void wgrad_f32_stg_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+template <bool CONV>
+__global__ __launch_bounds__(256, 2) void wgrad_f32_stg_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                               float* __restrict__ dw_part, float* __restrict__ db_part,
                                                               long part_stride, long R, int N, int K, int H, int W,
                                                               int Cin, long rows_per_split, int tiles_n, int tiles_k) {
-  using C = StgCfg<BN>;
-  constexpr int BK = C::BK, RS = C::RS, A_BYTES = C::A_BYTES, FST = C::FST, A_PW = C::A_PW, B_PW = C::B_PW;
+  using C = StgCfg;
+  constexpr int BN = C::BN, BK = C::BK, RS = C::RS, A_BYTES = C::A_BYTES, FST = C::FST, A_PW = C::A_PW, B_PW = C::B_PW;
   constexpr int A_CPR = C::A_CPR, B_CPR = C::B_CPR, A_RPI = C::A_RPI, B_RPI = C::B_RPI;
   constexpr int PLA = C::PLA, PLB = C::PLB, PST = C::PST, FN = C::FN, FK = C::FK;
   __shared__ __attribute__((aligned(16))) char F[2 * FST];
   __shared__ __attribute__((aligned(16))) char P[2 * PST];
 
-  const int wg = pipe::xcd_remap();
-  const int tk = wg % tiles_k;
-  const int tn = (wg / tiles_k) % tiles_n;
-  const int s = wg / (tiles_k * tiles_n);
-  const int n0 = tn * BN, k0 = tk * BK;
-  const long r_begin = static_cast<long>(s) * rows_per_split;
-  const long r_end = r_begin + rows_per_split < R ? r_begin + rows_per_split : R;
+  const WgTile T = wg_tile<BN, BK>(pipe::xcd_remap(), tiles_n, tiles_k, rows_per_split, R);
+  const int tk = T.tk, s = T.s, n0 = T.n0, k0 = T.k0;
+  const long r_begin = T.r_begin, r_end = T.r_end;
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wid / C::WK, wk = wid % C::WK;
   const int l32 = lane & 31, h = lane >> 5;
   const long HW = static_cast<long>(H) * W;
   const pipe::i32x4 yr = pipe::rsrc(dy, R * N * 4), xr = pipe::rsrc(x, CONV ? R * Cin * 4 : R * K * 4);
-  // waves past the dY stage's A_N DMA instructions (BN = 32) issue only their X pieces
-  const bool a_wave = A_PW * 4 == C::A_N || wid < C::A_N;
 
   // DMA pieces (the ring kernel's): fixed column per lane, row (within a step) per chunk
   const int a_col = n0 + 4 * (lane % A_CPR), b_col = k0 + 4 * (lane % B_CPR);
@@ -483,48 +436,35 @@ __global__ __launch_bounds__(256, StgCfg<BN>::OCC) void wgrad_f32_stg_kernel(con
   for (int c = 0; c < A_PW; ++c) a_row[c] = (wid + 4 * c) * A_RPI + lane / A_CPR;
 #pragma unroll
   for (int c = 0; c < B_PW; ++c) b_row[c] = (wid + 4 * c) * B_RPI + lane / B_CPR;
-  int b_c = b_col, b_dy = 0, b_dx = 0;
-  if (CONV) {
-    const int tap = b_col / Cin;
-    b_c = b_col - tap * Cin;
-    b_dy = tap / 3 - 1;
-    b_dx = tap % 3 - 1;
-  }
+  WgConvPiece<CONV> xp;
+  xp.init(b_col, Cin);
   const bool a_ok = a_col < N, b_ok = b_col < K;
-  int py[B_PW], px[B_PW];
-  const int adv_y = RS / W, adv_x = RS % W;
+  ImageCursor cur[B_PW];
+  const ImageCursor adv = ImageCursor::stride(RS, W);
   if (CONV) {
 #pragma unroll
-    for (int c = 0; c < B_PW; ++c) {
-      const int rem = static_cast<int>((r_begin + b_row[c]) % HW);
-      py[c] = rem / W;
-      px[c] = rem - py[c] * W;
-    }
+    for (int c = 0; c < B_PW; ++c) cur[c].init(r_begin + b_row[c], HW, W);
   }
   const long nsteps = r_end > r_begin ? (r_end - r_begin + RS - 1) / RS : 0;
   auto issue = [&](long kt) {
     char* st = F + (kt & 1) * FST;
     const long r0 = r_begin + kt * RS;
-    if (a_wave) {
 #pragma unroll
-      for (int c = 0; c < A_PW; ++c) {
-        const long r = r0 + a_row[c];
-        pipe::dma16(yr, st + (wid + 4 * c) * 1024,
-                    (kt < nsteps && a_ok && r < r_end) ? (static_cast<int>(r) * N + a_col) * 4 : pipe::kOOB);
-      }
+    for (int c = 0; c < A_PW; ++c) {
+      const long r = r0 + a_row[c];
+      pipe::dma16(yr, st + (wid + 4 * c) * 1024,
+                  (kt < nsteps && a_ok && r < r_end) ? (static_cast<int>(r) * N + a_col) * 4 : pipe::kOOB);
     }
 #pragma unroll
     for (int c = 0; c < B_PW; ++c) {
       const long r = r0 + b_row[c];
       int off = pipe::kOOB;
       if (CONV) {
-        const int yy = py[c] + b_dy, xx = px[c] + b_dx;
+        // the tap test is spelled out here: as a bool helper it moved two kernels' register allocation
+        const int yy = cur[c].y + xp.dy, xx = cur[c].x + xp.dx;
         if (kt < nsteps && b_ok && r < r_end && yy >= 0 && yy < H && xx >= 0 && xx < W)
-          off = ((static_cast<int>(r) + b_dy * W + b_dx) * Cin + b_c) * 4;
-        px[c] += adv_x;
-        py[c] += adv_y;
-        if (px[c] >= W) { px[c] -= W; ++py[c]; }
-        while (py[c] >= H) py[c] -= H;
+          off = xp.offset(static_cast<int>(r), W, Cin);
+        cur[c].advance(adv, H, W);
       } else if (kt < nsteps && b_ok && r < r_end) {
         off = (static_cast<int>(r) * K + b_col) * 4;
       }
@@ -533,10 +473,9 @@ __global__ __launch_bounds__(256, StgCfg<BN>::OCC) void wgrad_f32_stg_kernel(con
   };
 
   // split work of this thread: column sc of X, rows 8 sh .. 8 sh + 7 of the stage; column ac of dY (rows 8 ah ..)
-  // for the first 2 BN threads
   const int sc = tid & (BK - 1), sh = tid >> 7;
   const int ac = tid & (BN - 1), ah = tid / BN;
-  const bool a_split = tid < 2 * BN;
+  const bool a_split = tid < 256;
   const bool do_bias = db_part != nullptr && tk == 0;
   float bsum = 0.f;
   auto split_stage = [&](long j) {
@@ -577,8 +516,7 @@ __global__ __launch_bounds__(256, StgCfg<BN>::OCC) void wgrad_f32_stg_kernel(con
   if (nsteps > 0) {
     issue(0);
     issue(1);
-    if (a_wave) pipe::wait_vm<A_PW + B_PW>();          // this wave's pieces of step 0
-    else pipe::wait_vm<B_PW>();
+    pipe::wait_vm<A_PW + B_PW>();                      // this wave's pieces of step 0
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     split_stage(0);
@@ -634,17 +572,6 @@ __global__ __launch_bounds__(256, StgCfg<BN>::OCC) void wgrad_f32_stg_kernel(con
   }
 }
 
-// The 32-wide ring kernel is opt-in (APPLESTAR_WGRAD32_PIPE=1): on the learner's narrow convs it measured
-// 5-13 % slower than the register-staged kernel (76x80 64->32: 1358 vs 1283 us; 19x20 32->32: 66.7 vs
-// 59.2 us; profiles/r3v2_wgrad32_ab.jsonl) - 60 KB of stages hold it at 2 workgroups per CU.
-bool wgrad_f32_pipe32_off() {
-  static const bool off = [] {
-    const char* e = std::getenv("APPLESTAR_WGRAD32_PIPE");
-    return e == nullptr || e[0] != '1';
-  }();
-  return off;
-}
-
 // APPLESTAR_WGRAD_STG=0: the 128 x 128 tiles on the per-wave-split ring kernel instead of split-once staging
 bool wgrad_stg() {
   static const bool on = [] {
@@ -654,55 +581,39 @@ bool wgrad_stg() {
   return on;
 }
 
-// APPLESTAR_WGRAD_STG_NARROW=1: the 32 / 64-wide N tiles on split-once staging too.  Measured slower than the
-// per-wave-split kernels on every narrow learner shape (76x80 64 -> 32: 1266 vs 1142 us, 32 -> 64: 1142 vs 959 us;
-// fp32 step 55.25 / 55.35 vs 54.79 / 54.74 ms; profiles/r10b_wgrad32_stg_narrow_{on,off}.jsonl): off
-bool wgrad_stg_narrow() {
-  static const bool on = [] {
-    const char* e = std::getenv("APPLESTAR_WGRAD_STG_NARROW");
-    return e != nullptr && e[0] == '1';
-  }();
-  return on;
-}
-
+// split-MFMA mode: split-once staging for the 128 x 128 tile, the LDS-DMA ring for the other tiles of at least 64
+// outputs; the register-staged kernel for the 32-wide N tile and for the exact / per-wave-split modes.  (On the
+// narrow tiles the ring, a 256-wide K tile and split-once staging all measured slower: docs/PERF_LOG.md.)
 template <int BN, int BK, bool CONV>
 void launch(const float* dy, const float* x, float* dwp, float* dbp, long ps, long R, int N, int K, int H, int W,
             int Cin, int S, long rps, hipStream_t st) {
   const int tn = (N + BN - 1) / BN, tk = (K + BK - 1) / BK;
   const long nwg = static_cast<long>(tn) * tk * S;
-  if constexpr (BK == 128) {
-    if (f32_mfma_mode() == 1 && wgrad_stg() && (BN == 128 || wgrad_stg_narrow())) {
-      hipLaunchKernelGGL((wgrad_f32_stg_kernel<BN, CONV>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st, dy, x,
+  if constexpr (BN == 128 && BK == 128) {
+    if (f32_mfma_mode() == 1 && wgrad_stg()) {
+      hipLaunchKernelGGL((wgrad_f32_stg_kernel<CONV>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st, dy, x,
                          dwp, dbp, ps, R, N, K, H, W, Cin, rps, tn, tk);
       return;
     }
   }
-  if constexpr (BN >= 32 && (BK <= 128 || (BN == 128 && BK == 256))) {
-    if (f32_mfma_mode() == 1 && !(BN == 32 && wgrad_f32_pipe32_off())) {
+  if constexpr (BN >= 64) {
+    if (f32_mfma_mode() == 1) {
       hipLaunchKernelGGL((wgrad_f32_pipe_kernel<BN, BK, CONV, 3>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st,
                          dy, x, dwp, dbp, ps, R, N, K, H, W, Cin, rps, tn, tk);
       return;
     }
   }
-  if (f32_mfma_mode())
-    hipLaunchKernelGGL((wgrad_f32_kernel<BN, BK, CONV, 1>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st, dy, x,
-                       dwp, dbp, ps, R, N, K, H, W, Cin, rps, tn, tk);
-  else
-    hipLaunchKernelGGL((wgrad_f32_kernel<BN, BK, CONV, 0>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st, dy,
-                       x, dwp, dbp, ps, R, N, K, H, W, Cin, rps, tn, tk);
+  if constexpr (BK <= 128) {   // a 256-wide K tile is only picked in split-MFMA mode: the ring took it
+    if (f32_mfma_mode())
+      hipLaunchKernelGGL((wgrad_f32_kernel<BN, BK, CONV, 1>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st, dy,
+                         x, dwp, dbp, ps, R, N, K, H, W, Cin, rps, tn, tk);
+    else
+      hipLaunchKernelGGL((wgrad_f32_kernel<BN, BK, CONV, 0>), dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st, dy,
+                         x, dwp, dbp, ps, R, N, K, H, W, Cin, rps, tn, tk);
+  }
 }
 
 int pick(int n) { return n <= 32 ? 32 : (n <= 64 ? 64 : 128); }
-// A/B switch: the 32-wide N tile with a 256-wide K tile (each wave 32 x 64: the dY fragment feeds two MFMA
-// blocks) for K >= 256 (APPLESTAR_WGRAD32_BK=256).  Measured 20 % slower on the learner's narrow convs
-// (profiles/r3v6_wgrad32_bk256_ab.jsonl: 75 KB of stages, 2 workgroups per CU), so off by default.
-bool wgrad32_bk256() {
-  static const bool on = [] {
-    const char* e = std::getenv("APPLESTAR_WGRAD32_BK");
-    return e != nullptr && e[0] == '2';
-  }();
-  return on;
-}
 // APPLESTAR_WGRAD_WIDE=1: 128 x 256 tiles (each wave 64 x 128) for N >= 128, K >= 256 in split-MFMA mode
 bool wgrad_wide() {
   static const bool on = [] {
@@ -713,7 +624,7 @@ bool wgrad_wide() {
 }
 // the K tile: a wave covers >= 32 columns (2 waves along K for BN >= 64, 4 for the 32-wide N tile)
 int pick_k(int k, int bn) {
-  if (bn == 32) return (k >= 256 && wgrad32_bk256()) ? 256 : 128;
+  if (bn == 32) return 128;
   if (bn == 128 && k >= 256 && wgrad_wide() && f32_mfma_mode() == 1) return 256;
   return k <= 64 ? 64 : 128;
 }
@@ -777,7 +688,7 @@ void wgrad_f32(const float* dy, const float* x, float* dw_part, float* db_part, 
     else launch<BNv, BKv, false>(dy, x, dw_part, db_part, part_stride, R, N, K, H, W, Cin, S, rps, st);     \
     return;                                                                                \
   }
-  AS_WGF(128, 128) AS_WGF(128, 64) AS_WGF(64, 128) AS_WGF(64, 64) AS_WGF(32, 128) AS_WGF(32, 256) AS_WGF(128, 256)
+  AS_WGF(128, 128) AS_WGF(128, 64) AS_WGF(64, 128) AS_WGF(64, 64) AS_WGF(32, 128) AS_WGF(128, 256)
 #undef AS_WGF
 }
 

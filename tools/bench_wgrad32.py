@@ -1,7 +1,7 @@
-"""fp32 weight gradients with a <= 32-wide output (N tile 32): time per call and error vs float64 on a row
-subsample, for the A/B of the 32-wide LDS-DMA ring kernel (run once with APPLESTAR_WGRAD32_PIPE=0 for the
-register-staged kernel, APPLESTAR_WGRAD32_PIPE=1 for the ring; the switch is read once per process).
-Round 6: the split-once staging kernel for 32 / 64-wide N tiles is the default (APPLESTAR_WGRAD_STG_NARROW=0: off).
+"""fp32 weight gradients with a narrow output (N tile 32 / 64): time per call and error vs float64 on a row
+subsample, under the default dispatch of split-MFMA mode - the halo-window kernels for the convs they take
+(APPLESTAR_CONV_WGRAD_HALO_F32=0: the per-tap kernels of wgrad_f32.hip instead; read once per process), the
+register-staged 32-wide and the ring 64-wide tiles for the rest.
 
     python tools/bench_wgrad32.py > out.jsonl
 """
@@ -30,11 +30,7 @@ def main():
     from applestar_amd.ops import native
     C = native.ensure_loaded()
     C.set_f32_mfma_mode(1)
-    mode = 'ring' if os.environ.get('APPLESTAR_WGRAD32_PIPE', '0') == '1' else 'regstaged'
-    if os.environ.get('APPLESTAR_WGRAD_STG_NARROW', '1') != '0':
-        mode = 'stg_narrow'
-    if os.environ.get('APPLESTAR_WGRAD32_BK', '128') == '256':
-        mode += '_bk256'
+    mode = 'halo%d' % C.conv_wgrad_halo_f32_mode()
     torch.manual_seed(0)
     for B, H, W, cin, cout in CONV:
         x = torch.randn(B, H, W, cin, device='cuda')
