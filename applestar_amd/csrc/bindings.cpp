@@ -1392,7 +1392,8 @@ void fused_clip_adam(const at::Tensor& table, const at::Tensor& chunks, const at
                      const c10::optional<at::Tensor>& gate, const at::Tensor& norm_out, double max_norm,
                      const c10::optional<at::Tensor>& mom, const c10::optional<at::Tensor>& scale,
                      const c10::optional<at::Tensor>& mom_init, const c10::optional<at::Tensor>& hp, double lr_bc1, double b1, double b2, double inv_sqrt_bc2,
-                     double eps, double wd, bool decoupled) {
+                     double eps, double wd, bool decoupled, const c10::optional<at::Tensor>& guard_gate,
+                     const c10::optional<at::Tensor>& guard_status, const c10::optional<at::Tensor>& guard_counters) {
   check_cuda(table, "table");
   TORCH_CHECK(table.scalar_type() == at::kLong && chunks.scalar_type() == at::kLong && table.is_contiguous() &&
               chunks.is_contiguous() && table.numel() % 6 == 0 && chunks.numel() % 2 == 0, "fused_clip_adam: tables");
@@ -1424,13 +1425,33 @@ void fused_clip_adam(const at::Tensor& table, const at::Tensor& chunks, const at
     TORCH_CHECK(hp->scalar_type() == at::kFloat && hp->numel() == 3 && hp->is_cuda(), "fused_clip_adam: hp fp32 [3]");
     hpp = hp->data_ptr<float>();
   }
+  // the non-finite guard: all three buffers or none
+  float* ggp = nullptr;
+  int* gsp = nullptr;
+  int* gcp = nullptr;
+  const bool guard = guard_status && guard_status->defined();
+  TORCH_CHECK(guard == (guard_gate && guard_gate->defined()) && guard == (guard_counters && guard_counters->defined()),
+              "fused_clip_adam: the guard needs its gate, status and counters together");
+  if (guard) {
+    TORCH_CHECK(guard_gate->scalar_type() == at::kFloat && guard_gate->numel() == 1 && guard_gate->is_cuda() &&
+                guard_gate->device() == table.device(), "fused_clip_adam: guard gate fp32 [1] on the device");
+    TORCH_CHECK(guard_status->scalar_type() == at::kInt && guard_status->numel() == 3 && guard_status->is_cuda() &&
+                guard_status->is_contiguous() && guard_status->device() == table.device(),
+                "fused_clip_adam: guard status int32 [3] on the device");
+    TORCH_CHECK(guard_counters->scalar_type() == at::kInt && guard_counters->numel() == 2 && guard_counters->is_cuda() &&
+                guard_counters->is_contiguous() && guard_counters->device() == table.device(),
+                "fused_clip_adam: guard counters int32 [2] on the device");
+    ggp = guard_gate->data_ptr<float>();
+    gsp = guard_status->data_ptr<int>();
+    gcp = guard_counters->data_ptr<int>();
+  }
   c10::hip::HIPGuard g(table.device().index());
   as::fused_clip_adam(table.data_ptr(), reinterpret_cast<const long*>(chunks.data_ptr<int64_t>()),
                       static_cast<int>(nch), static_cast<int>(nt), part.data_ptr<float>(), gp,
                       norm_out.data_ptr<float>(), static_cast<float>(max_norm), mp, sp, ip, hpp,
                       static_cast<float>(lr_bc1), static_cast<float>(b1), static_cast<float>(b2),
                       static_cast<float>(inv_sqrt_bc2), static_cast<float>(eps), static_cast<float>(wd),
-                      decoupled ? 1 : 0, stream());
+                      decoupled ? 1 : 0, ggp, gsp, gcp, stream());
 }
 
 // ---------------------------------------------------------------- fp32 conv3x3 / weight gradients
@@ -2885,7 +2906,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_f32_epi2", &conv3x3_f32_epi2);
   m.def("conv3x3_f32_epi2_supported", &conv3x3_f32_epi2_supported);
   m.def("conv3x3_f32", &conv3x3_f32);
-  m.def("fused_clip_adam", &fused_clip_adam);
+  m.def("fused_clip_adam", &fused_clip_adam, py::arg("table"), py::arg("chunks"), py::arg("part"), py::arg("gate"),
+        py::arg("norm_out"), py::arg("max_norm"), py::arg("mom"), py::arg("scale"), py::arg("mom_init"), py::arg("hp"),
+        py::arg("lr_bc1"), py::arg("b1"), py::arg("b2"), py::arg("inv_sqrt_bc2"), py::arg("eps"), py::arg("wd"),
+        py::arg("decoupled"), py::arg("guard_gate") = py::none(), py::arg("guard_status") = py::none(),
+        py::arg("guard_counters") = py::none());
   m.def("head_sample", &head_sample);
   m.def("target_unit_sample", &target_unit_sample);
   m.def("fused_adam_chunk", &as::fused_adam_chunk);

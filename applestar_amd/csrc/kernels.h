@@ -321,10 +321,14 @@ int fused_adam_chunk();
 // table: per tensor {p, g, m, v, numel, first chunk} (int64 x 6); chunks: per chunk {tensor, offset} (int64 x 2).
 // mom / scale (fp32 [ntensors]) non-null: momentum_norm clip with threshold max_norm; else pytorch_norm at
 // max_norm (0 = no clip).  hp (fp32 [3] = lr / bc1, 1 / sqrt(bc2), wd) non-null overrides those arguments.
+// guard_status (int32 [3] = skipped, first bad chunk or -1, bad chunks) non-null: the non-finite guard - one more
+// one-workgroup launch scans part[] and writes the status, guard_gate (fp32 [1]: gate open AND all partials
+// finite; the update reads it in place of gate) and guard_counters (int32 [2] = guarded skips in total, in a
+// row; incremented in place).  All three null: the launches and results are those without the guard.
 void fused_clip_adam(const void* table, const long* chunks, int nchunks, int ntensors, float* part,
                      const float* gate, float* norm_out, float max_norm, float* mom, float* scale, float* mom_init,
                      const float* hp, float lr_bc1, float b1, float b2, float inv_sqrt_bc2, float eps, float wd,
-                     int decoupled, hipStream_t s);
+                     int decoupled, float* guard_gate, int* guard_status, int* guard_counters, hipStream_t s);
 
 // ---- wgrad.hip ---------------------------------------------------------------------------------
 // dw_part [S, N, K] / db_part [S, N] fp32 partials of dW = dY^T X(r, k), db = sum_r dY; dy [R, N] bf16.

@@ -20,6 +20,12 @@
 // A step whose device gate is 0 (a timed-out LSTM exchange on any rank: the gate is all-reduced with the
 // gradients) leaves p, m, v and the momentum EMA untouched: the update is skipped, not multiplied by 0
 // (NaN * 0 is NaN, and v would still decay).
+// Non-finite guard (opt-in; absent, the launches above are all there is): mt_guard, one workgroup between 1 and
+// 2 / 3, scans part[] and turns "some chunk's sum of squares is not finite" into the same gate - the later
+// kernels get the guard's EFFECTIVE gate (incoming gate open AND every partial finite) in place of the caller's,
+// so a guarded skip is the gated skip above.  It also leaves a per-step status (skipped, first bad chunk, number
+// of bad chunks) and two running counters (guarded skips in total / in a row) on the device; nothing is read
+// back by the host.
 // The per-tensor pointer table is built once on the host (parameters, gradients and moments never move), so
 // a step passes two device pointers.  The step-dependent scalars (lr / bc1, 1 / sqrt(bc2), decoupled decay)
 // come either as kernel arguments (eager step) or from a 3-float device buffer that the host refreshes before
@@ -77,6 +83,56 @@ __global__ __launch_bounds__(kOptT) void mt_sumsq_kernel(const TensorRec* __rest
   }
   s = block_sum(s, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// Non-finite guard: one workgroup over part[0 .. nchunks) (a few KB), after mt_sumsq.  A chunk is bad when its
+// sum of squares is NaN or Inf: a NaN / Inf gradient element makes it so, and so - on purpose - does a finite
+// gradient whose square overflows fp32 (|g| > ~1.8e19): the norm would be Inf, the clip coefficient 0 and the
+// step wasted (and without a clip the overflowed square would go straight into v).
+//   eff_gate[0] = 1 when the incoming gate is absent or open AND no chunk is bad, else 0: the later kernels
+//                 read it in place of the caller's gate;
+//   status      = {skipped (0 / 1: some chunk is bad, whatever the incoming gate), first bad chunk or -1,
+//                  number of bad chunks};
+//   counters    = {guarded skips in total, guarded skips in a row (zeroed by any step that is not one)}.
+// Counting and the minimum are integer reductions: the result does not depend on their order, and part[] is
+// identical on every rank (mt_sumsq's fixed order over all-reduced gradients), so every rank decides the same.
+__global__ __launch_bounds__(kOptT) void mt_guard_kernel(const float* __restrict__ part, int nchunks,
+                                                         const float* __restrict__ gate, float* __restrict__ eff_gate,
+                                                         int* __restrict__ status, int* __restrict__ counters) {
+  __shared__ int red_n[kOptT / 64], red_f[kOptT / 64];
+  int n = 0, first = nchunks;
+  for (int i = threadIdx.x; i < nchunks; i += kOptT) {
+    if ((__float_as_uint(part[i]) & 0x7f800000u) == 0x7f800000u) {   // exponent all ones: NaN or +-Inf
+      if (n == 0) first = i;
+      ++n;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n += __shfl_xor(n, o, kWave);
+    const int f = __shfl_xor(first, o, kWave);
+    first = f < first ? f : first;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red_n[threadIdx.x >> 6] = n;
+    red_f[threadIdx.x >> 6] = first;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    n = 0;
+    first = nchunks;
+    for (int w = 0; w < kOptT / 64; ++w) {
+      n += red_n[w];
+      first = red_f[w] < first ? red_f[w] : first;
+    }
+    const int bad = n > 0 ? 1 : 0;
+    status[0] = bad;
+    status[1] = bad ? first : -1;
+    status[2] = n;
+    eff_gate[0] = (!bad && !gated_off(gate)) ? 1.f : 0.f;
+    counters[0] += bad;
+    counters[1] = bad ? counters[1] + 1 : 0;
+  }
 }
 
 __global__ __launch_bounds__(kOptT) void mt_momentum_clip_kernel(const TensorRec* __restrict__ tt, int ntensors,
@@ -164,10 +220,15 @@ int fused_adam_chunk() { return kChunk; }
 void fused_clip_adam(const void* table, const long* chunks, int nchunks, int ntensors, float* part,
                      const float* gate, float* norm_out, float max_norm, float* mom, float* scale, float* mom_init,
                      const float* hp, float lr_bc1, float b1, float b2, float inv_sqrt_bc2, float eps, float wd,
-                     int decoupled, hipStream_t s) {
+                     int decoupled, float* guard_gate, int* guard_status, int* guard_counters, hipStream_t s) {
   if (nchunks <= 0) return;
   const TensorRec* tt = static_cast<const TensorRec*>(table);
   hipLaunchKernelGGL(mt_sumsq_kernel, dim3(nchunks), dim3(kOptT), 0, s, tt, chunks, part);
+  if (guard_status != nullptr) {   // the non-finite guard: its effective gate replaces the caller's from here on
+    hipLaunchKernelGGL(mt_guard_kernel, dim3(1), dim3(kOptT), 0, s, static_cast<const float*>(part), nchunks, gate,
+                       guard_gate, guard_status, guard_counters);
+    gate = guard_gate;
+  }
   if (mom != nullptr) {
     hipLaunchKernelGGL(mt_momentum_clip_kernel, dim3(1), dim3(kOptT), 0, s, tt, ntensors, part, max_norm, mom, scale,
                        mom_init, gate, norm_out);

@@ -30,7 +30,8 @@ DEFAULT_BASE_LEARNER_CONFIG = {
     'learner': {'load_path': '', 'use_cuda': True, 'use_distributed': False, 'max_iterations': int(1e8),
                 'learning_rate': 1e-3, 'weight_decay': 1e-4, 'data': {'batch_size': 1, 'trajectory_length': 64},
                 'grad_clip': {'type': 'none', 'threshold': 1.4}, 'hook': DEFAULT_HOOK_CONFIG,
-                'player_id': 'MP0', 'log_to_stdout': True, 'accumulate_steps': 1},
+                'player_id': 'MP0', 'log_to_stdout': True, 'accumulate_steps': 1,
+                'nonfinite_guard': False, 'max_consecutive_skips': 10},
 }
 
 
@@ -185,15 +186,39 @@ class BaseLearner:
         keys = [k for k, v in info.items() if torch.is_tensor(v) and v.numel() == 1]
         if keys:
             vals = torch.stack([info[k].detach().float().reshape(()) for k in keys]).cpu().tolist()
-            self.log_buffer.update(dict(zip(keys, vals)))
+            got = dict(zip(keys, vals))
+            self.log_buffer.update(got)
             if self.log_buffer.get('lstm_exchange_ok', 1.0) == 0.0:
                 # the split LSTM recurrence's cross-workgroup exchange timed out: this step's update was gated
                 # to zero on the device (trainer._lstm_gate); stop rather than train on garbage
                 raise RuntimeError('LSTM split-recurrence exchange timed out (lstm.hip kSplitPollLimit); '
                                    'the update of this iteration was dropped')
+            if 'update_skipped' in got:
+                self._note_update_skipped(got)
         for k, v in info.items():
             if isinstance(v, (int, float)):
                 self.log_buffer[k] = float(v)
+
+    def _note_update_skipped(self, got: Dict):
+        """The non-finite guard's policy (``learner.nonfinite_guard``): ``got`` holds this iteration's fetched
+        ``update_skipped`` / ``skipped_updates`` / ``nonfinite_at``.  A skipped update (the weights and the optimizer
+        state were left alone on the device, on every rank alike) is logged with the offending parameter's name;
+        ``learner.max_consecutive_skips`` of them in a row (0 = never) end the run - the gradients are then
+        not coming back, and the checkpoint that ``run`` saves on the way out still holds finite weights."""
+        if got['update_skipped'] != 1.0:
+            self._consecutive_skips = 0
+            return
+        self._consecutive_skips = getattr(self, '_consecutive_skips', 0) + 1
+        name_of = getattr(self.trainer, 'nonfinite_name', None)
+        name = name_of(int(got.get('nonfinite_at', -1))) if name_of is not None else ''
+        total = int(got.get('skipped_updates', self._consecutive_skips))
+        self.logger.warning(f'iteration {self.last_iter.val}: non-finite gradient in {name or "<unknown>"}; the update '
+                            f'was skipped ({self._consecutive_skips} in a row, {total} in total)')
+        limit = int(self.cfg.learner.get('max_consecutive_skips', 10))
+        if 0 < limit <= self._consecutive_skips:
+            raise RuntimeError(f'{self._consecutive_skips} consecutive updates skipped for non-finite gradients '
+                               f'(learner.max_consecutive_skips = {limit}); last in {name or "<unknown>"} at '
+                               f'iteration {self.last_iter.val}')
 
     def close(self):
         pass

@@ -39,6 +39,10 @@ DEFAULT_LEARNER_CONFIG = AttrDict({
         # gradient accumulation: micro-batches per optimizer update (the learner loop draws this many batches per
         # iteration; micro_step on all but the last).  Not available with graph_step
         'accumulate_steps': 1,
+        # skip an update whose gradients hold a NaN / Inf, decided on the device (runtime/train_engine.py); the
+        # learner logs the offending parameter and stops after max_consecutive_skips such updates in a row (0 = never)
+        'nonfinite_guard': False,
+        'max_consecutive_skips': 10,
     },
     'model': {'enable_baselines': ['winloss']},
 })

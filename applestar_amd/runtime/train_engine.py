@@ -17,7 +17,18 @@ in the forward + loss and in the optimizer's hyper-parameters.  Here everything 
 * the LSTM-exchange health gate: the split LSTM recurrence raises a device flag when its cross-workgroup
   exchange times out; the flag is MIN-reduced across ranks together with the gradients, so EVERY rank skips
   the same step (a rank-local skip would let the replicas' weights diverge), and the fused update returns
-  before touching the weights or the optimizer state.
+  before touching the weights or the optimizer state;
+* the non-finite guard (``learner.nonfinite_guard``, off by default): the same gate driven by the gradients
+  themselves.  The decision is taken in ``_update``, i.e. after ``_reduce``, on gradients that are identical on
+  every rank, so every rank skips the same step without a further collective.  Fused path: one extra
+  one-workgroup launch (optim.hip ``mt_guard``) and an EXACT skip - weights, moments and the clip's EMA keep their
+  bits.  Torch path (CPU, or a configuration ``FusedClipAdam.supported`` rejects): one ``_foreach_norm`` and an
+  ``isfinite`` folded into the gate that ``GradClip.apply`` already takes, which keeps that gate's contract - the
+  gradients are selected to zero and ``optimizer.step()`` still runs, so the skip is exact only for an optimizer
+  that leaves its parameters alone on a zero gradient (the RL learner's Adam: beta1 = 0, no weight decay).
+  Either way the host-side Adam step count and the LR scheduler advance on a skipped step, as on a gated one, and
+  with gradient accumulation a non-finite micro-batch makes the window's sum non-finite: the whole window is one
+  skipped update.  The running counters are zeroed by ``reset_optimizer`` and belong to no ``state_dict``.
 """
 from __future__ import annotations
 
@@ -107,6 +118,8 @@ class TrainEngine:
         # the step's health gate lives in ONE device scalar: a captured update graph reads it by address
         self._gate = torch.ones((), dtype=torch.float32, device=self.device) if self.device.type == 'cuda' else None
         self.graph = None
+        # skip updates whose gradients are not finite, on the device (module docstring)
+        self.nonfinite_guard = bool(lc.get('nonfinite_guard', False))
         # gradient accumulation (backward(more=True)): micro-batches summed into the flat gradient buffers so far;
         # 0 = no window open.  The partial sum lives only in those buffers, never in a state_dict
         self._window = 0
@@ -142,7 +155,14 @@ class TrainEngine:
             self.fused_opt = FusedClipAdam(self.optimizer, self.grad_clip.threshold
                                            if self.grad_clip.clip_type not in ('none', 'momentum_norm') else None,
                                            clip=self.grad_clip, device_hparams=self._graph_requested(),
-                                           segments=segments)
+                                           segments=segments, guard=self.nonfinite_guard)
+        # the torch path's guard state (the fused optimizer owns its own): last step's status and the running
+        # counters, int32 device tensors with the fused path's meaning; fresh, i.e. zeroed, with the optimizer
+        self._guard_status = None
+        self._guard_counters = None
+        if self.nonfinite_guard and self.fused_opt is None:
+            self._guard_counters = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self._names = None
         if getattr(self, 'graph', None) is not None:
             self.graph.reset()
 
@@ -240,6 +260,8 @@ class TrainEngine:
                 self.grad_clip.step += 1
             norm = self.fused_opt.step(gate)
         else:
+            if self.nonfinite_guard:
+                gate = self._torch_guard(gate)
             norm = self.grad_clip.apply(self.opt_params, gate=gate)
             self.optimizer.step()
         if self.master is not None:
@@ -247,6 +269,27 @@ class TrainEngine:
         elif self.derived is not None:
             self.derived.refresh()
         return norm
+
+    @torch.no_grad()
+    def _torch_guard(self, gate: Optional[torch.Tensor]) -> torch.Tensor:
+        """The non-finite guard of the torch path: the incoming gate (created where there is none, as on the CPU)
+        times "the sum of the tensors' squared gradient norms is finite", without a host read.  A squared norm
+        that overflows fp32 counts as non-finite, as in the fused path.  Leaves the step's status (skipped, index
+        of the first tensor with a non-finite squared norm or -1, number of such tensors) and advances the
+        counters.  ``self._gate`` itself (logged as ``lstm_exchange_ok``) is not touched."""
+        grads = [p.grad for p in self.opt_params if p.grad is not None]
+        sq = torch.stack(torch._foreach_norm(grads)).float().square()
+        bad = ~torch.isfinite(sq)
+        ok = torch.isfinite(sq.sum())
+        skipped = (~ok).to(torch.int32)
+        n_bad = bad.sum()
+        first = torch.where(n_bad > 0, bad.to(torch.int32).argmax(), -1)      # argmax: the first of equal maxima
+        self._guard_status = torch.stack([skipped, first.to(torch.int32), n_bad.to(torch.int32)])
+        c = self._guard_counters
+        c[0].add_(skipped)
+        c[1].add_(1).mul_(skipped)
+        ok = ok.to(torch.float32)
+        return ok if gate is None else gate.reshape(()).float() * ok
 
     # ------------------------------------------------------------------ diagnostics / state
     def nonfinite_grads(self):
@@ -263,6 +306,48 @@ class TrainEngine:
                 if p.grad is not None and not bool(torch.isfinite(p.grad).all()):
                     bad.append(n)
         return bad
+
+    def _name_of(self, p, offset: int = 0) -> str:
+        """Name of the model parameter behind optimizer parameter ``p``; for the bf16 learner's flat fp32 master,
+        of the parameter whose range (``MasterWeights.segments()``) contains element ``offset``."""
+        if self._names is None:
+            names = dict(self.master.names) if self.master is not None else \
+                {q: n for n, q in self.model.named_parameters()}
+            starts, owners = [], []
+            if self.master is not None:
+                order = [self.master.names[q] for b, _, _ in self.master._slices for q in b.params]
+                for (off, _), n in zip(self.master.segments(), order):
+                    starts.append(off)
+                    owners.append(n)
+            self._names = (names, starts, owners)
+        names, starts, owners = self._names
+        if self.master is not None and p is self.master.master:
+            import bisect
+            i = bisect.bisect_right(starts, int(offset)) - 1
+            return owners[i] if i >= 0 else ''
+        return names.get(p, '')
+
+    def nonfinite_name(self, index) -> str:
+        """Parameter name for a ``nonfinite_at`` value of :meth:`step_info` ('' for -1: nothing was non-finite).
+        No device work: the fused path looks the chunk up in the optimizer's host copy of its chunk table.
+
+        * fp32 fused path: the chunk's table row is the parameter;
+        * bf16 master fused path: the row may be the whole flat master (``pytorch_norm``) - the name is then that
+          of the parameter containing the chunk's first element; the offending element lies within one chunk
+          (``fused_adam_chunk()`` elements) after it, so it may belong to a small parameter that follows;
+        * torch path: the index counts the optimizer's tensors that have a gradient (the flat master is one)."""
+        index = int(index)
+        if index < 0:
+            return ''
+        if self.fused_opt is not None:
+            row, off = self.fused_opt.locate(index)
+            p, off0 = self.fused_opt.row_origin(row)
+            return self._name_of(p, off0 + off)
+        with_grad = [p for p in self.opt_params if p.grad is not None]
+        p = with_grad[index]
+        if self.master is not None and p is self.master.master:
+            return '<fp32 master>'
+        return self._name_of(p)
 
     def model_state_dict(self):
         """fp32 model weights (the master copies when the compute weights are bf16)."""
@@ -302,4 +387,16 @@ class TrainEngine:
     def step_info(self, info: Dict) -> Dict:
         if self._gate is not None:
             info['lstm_exchange_ok'] = self._gate
+        if self.nonfinite_guard:
+            # device scalars (the learner fetches them in its one transfer per iteration): was this update skipped
+            # for non-finite gradients, the running total of such skips, and where - nonfinite_name() decodes it
+            fo = self.fused_opt
+            status, counters = (fo.status, fo.counters) if fo is not None else \
+                (self._guard_status, self._guard_counters)
+            if status is not None:
+                if fo is not None and fo.device_hparams:
+                    status = status.clone()      # the graph-replayed update's status is one static buffer
+                info['update_skipped'] = status[0]
+                info['skipped_updates'] = counters[0]      # a view of the live counter: read it before the next step
+                info['nonfinite_at'] = status[1]
         return info

@@ -28,6 +28,8 @@ DEFAULT_SL_CONFIG = AttrDict({
         'amp_dtype': None,        # fp32 like the reference; 'bfloat16' = bf16 compute with fp32 masters
         'deterministic': False,   # ordered kernels where they exist (ops.set_deterministic); only ever turns the mode on
         'accumulate_steps': 1,    # gradient accumulation: chunks per optimizer update (micro_step on all but the last)
+        'nonfinite_guard': False,        # skip updates with NaN / Inf gradients on the device (runtime/train_engine.py)
+        'max_consecutive_skips': 10,     # the learner stops after this many skipped updates in a row (0 = never)
     },
 })
 

@@ -13,6 +13,15 @@ A zero device ``gate`` (timed-out LSTM exchange) skips the update in the kernel:
 momentum EMA keep their values.  ``device_hparams=True`` reads lr / bias corrections / decay from a 3-float device
 buffer refreshed before each step (for HIP-graph replay: the graph keeps the buffer's address, not the values).
 
+``guard=True`` (the learners' ``nonfinite_guard``) adds one one-workgroup launch that drives the same gate from the
+gradients themselves: a step whose gradients hold a NaN / Inf (or a finite value whose square overflows fp32) is
+skipped exactly like a gated one, with no host read.  ``status`` (int32 [3]: skipped, first bad chunk or -1, number
+of bad chunks) describes the last step, ``counters`` (int32 [2]: guarded skips in total, in a row) run on the
+device, and :meth:`FusedClipAdam.locate` maps a chunk index to its tensor from a host copy of the chunk table.
+With finite gradients the guarded step's results are bit-identical to the unguarded one's; the returned norm of a
+skipped step is what the kernels computed (NaN / Inf).  The host-side step count (bias corrections) and any LR
+scheduler advance on a skipped step, as they do on a gated one.
+
 The moments ARE the wrapped ``torch.optim.Adam``'s own ``exp_avg`` / ``exp_avg_sq`` state tensors and the
 step count its ``step``, so ``optimizer.state_dict()`` / ``load_state_dict`` (checkpoints, league resets) are
 unchanged and either path can continue the other's run.  Learning rate and weight decay are read from the
@@ -32,7 +41,7 @@ def _capturing() -> bool:
 
 
 class FusedClipAdam:
-    """``FusedClipAdam(optimizer, max_norm, clip=None, device_hparams=False, segments=None)``.
+    """``FusedClipAdam(optimizer, max_norm, clip=None, device_hparams=False, segments=None, guard=False)``.
 
     ``segments``: {optimizer param: [(offset, numel), ...]} splits a flat parameter (the bf16 learner's fp32
     master, parallel/mixed.py) into its per-layer pieces, so per-tensor clips (momentum_norm) see the same
@@ -43,8 +52,15 @@ class FusedClipAdam:
     HP_RING = 32       # pinned host slots of the device-hyperparameter upload (see prepare)
 
     def __init__(self, optimizer: torch.optim.Optimizer, max_norm: Optional[float], clip=None,
-                 device_hparams: bool = False, segments: Optional[Dict] = None):
+                 device_hparams: bool = False, segments: Optional[Dict] = None, guard: bool = False):
         self.opt = optimizer
+        # the non-finite guard (module docstring); off: no buffer is allocated and the launches are unchanged
+        self.guard = bool(guard)
+        self.status = None         # int32 [3] of the last step: skipped, first bad chunk or -1, bad chunks
+        self.counters = None       # int32 [2], persistent: guarded skips in total, in a row
+        self._guard_gate = None
+        self._status_static = None
+        self._chunks_host, self._origin = [], []      # host copies of the chunk table / the rows' parameters
         self.max_norm = float(max_norm) if max_norm else 0.0
         # only the 'ema' form of momentum_norm scales per tensor; its 'reference' form (the reference's effective
         # behaviour, utils/grad_clip.py) is an unclipped step reporting the global norm
@@ -96,7 +112,7 @@ class FusedClipAdam:
         C = native.ensure_loaded()
         chunk = C.fused_adam_chunk()
         st = self.opt.state
-        rows, chunks = [], []
+        rows, chunks, origin = [], [], []
         for p in params:
             s = st[p]
             if 'exp_avg' not in s:                       # torch.optim.Adam's lazy state, created the same way
@@ -112,10 +128,18 @@ class FusedClipAdam:
             for off0, n in self.segments.get(p, [(0, p.numel())]):
                 t = len(rows) // 6
                 rows += [x.data_ptr() + 4 * off0 for x in xs] + [n, len(chunks) // 2]
+                origin.append((p, off0))
                 for off in range(0, n, chunk):
                     chunks += [t, off]
         dev = params[0].device
         self.ntensors = len(rows) // 6
+        # host copies: chunk -> (row, offset) for locate(), row -> (parameter, offset of the row in it)
+        self._chunks_host, self._origin = chunks, origin
+        if self.guard and (self.counters is None or self.counters.device != dev):
+            # allocated with the table, i.e. before any capture; a rebuilt table keeps the running counters
+            self.counters = torch.zeros(2, dtype=torch.int32, device=dev)
+            self._guard_gate = torch.ones(1, dtype=torch.float32, device=dev)
+            self._status_static = torch.tensor([0, -1, 0], dtype=torch.int32, device=dev)
         self._table = torch.tensor(rows, dtype=torch.int64, device=dev)
         self._chunks = torch.tensor(chunks, dtype=torch.int64, device=dev)
         self._part = torch.empty(len(chunks) // 2, dtype=torch.float32, device=dev)
@@ -136,6 +160,20 @@ class FusedClipAdam:
         if self._table is None or sig != self._sig:
             self._build(params)
             self._sig = self._signature(params)
+
+    def locate(self, chunk_index: int):
+        """``(tensor_row, element offset of the chunk's start in that row)`` of a chunk index, e.g. the guard's
+        ``first_bad``, from the host copy of the chunk table (no device read).  A row is a parameter, or one of its
+        ``segments``; the chunk covers ``[offset, min(offset + fused_adam_chunk(), row numel))``."""
+        i = int(chunk_index)
+        if not 0 <= i < len(self._chunks_host) // 2:
+            raise IndexError(f'FusedClipAdam.locate: chunk {i} of {len(self._chunks_host) // 2}')
+        return self._chunks_host[2 * i], self._chunks_host[2 * i + 1]
+
+    def row_origin(self, tensor_row: int):
+        """``(optimizer parameter, element offset of the row inside it)`` of a table row (offset 0 unless the
+        parameter was given ``segments``)."""
+        return self._origin[int(tensor_row)]
 
     def hparams(self):
         """(lr / bc1, 1 / sqrt(bc2), decay, decoupled) of the NEXT step; advances the step count."""
@@ -217,9 +255,17 @@ class FusedClipAdam:
             mom, init = c.momentum_state(self.ntensors, dev)
             scale = self._scale
         norm = torch.empty((), dtype=torch.float32, device=self._part.device)   # per step: callers may keep it
+        guard = ()
+        if self.guard:
+            # per step like the norm, so callers may keep it; an update that may be replayed from a graph
+            # (device_hparams) writes ONE static buffer, eagerly or from whichever graph replays: read it (or clone
+            # it) before the next step
+            self.status = self._status_static if self.device_hparams else \
+                torch.empty(3, dtype=torch.int32, device=self._part.device)
+            guard = (self._guard_gate, self.status, self.counters)
         self._C.fused_clip_adam(self._table, self._chunks, self._part,
                                 gate.reshape(1).float() if gate is not None else None, norm.view(1),
                                 self.clip.threshold if self.clip is not None else self.max_norm, mom, scale, init,
                                 self._hp if self.device_hparams else None, lr_bc1, b1, b2, inv_sqrt_bc2,
-                                float(g['eps']), wd, decoupled)
+                                float(g['eps']), wd, decoupled, *guard)
         return norm
