@@ -722,8 +722,11 @@ std::vector<at::Tensor> su_sample(const at::Tensor& key, const at::Tensor& c0, c
                                   const at::Tensor& be1, double temperature, double eps, int64_t max_steps,
                                   bool extra_units) {
   for (auto* t : {&key, &c0, &u, &entity_num, &su_mask, &wf, &bf, &wq2, &bq2, &wih, &whh, &lni_w, &lni_b, &lnh_w,
-                  &lnh_b, &lnc_w, &lnc_b, &we1, &be1})
+                  &lnh_b, &lnc_w, &lnc_b, &we1, &be1}) {
     check_cuda(*t, "su_sample input");
+    // the kernels index every input densely (and read wf / wq2 / wih / whh in 16-byte vectors)
+    TORCH_CHECK(t->is_contiguous(), "su_sample: inputs must be contiguous");
+  }
   const int64_t B = key.size(0), N1 = key.size(1);
   TORCH_CHECK(key.dim() == 3 && key.size(2) == 32, "su_sample: key must be [B, N+1, 32]");
   TORCH_CHECK(N1 >= 1 && N1 <= 513, "su_sample: N+1 must be in [1, 513]");

@@ -64,23 +64,34 @@ __device__ __forceinline__ int sample_row(const float* __restrict__ row, int C, 
   float excl = __shfl_up(incl, 1, kWave);   // the neighbour's inclusive value exactly: no gap / overlap by rounding
   if (lane == 0) excl = 0.f;
   if (lane == 63) scan[wv] = incl;
-  __shared__ int pick;
-  if (threadIdx.x == 0) pick = C - 1;
+  __shared__ int pick, owner;
+  if (threadIdx.x == 0) {
+    pick = C - 1;
+    owner = -1;
+  }
   __syncthreads();
   float woff = 0.f;
   for (int w = 0; w < wv; ++w) woff += scan[w];
   const float total = scan[0] + scan[1] + scan[2] + scan[3];
   const float target = u * total;
-  incl += woff;
   const float before = excl + woff;
-  if (s0 < s1 && incl > target && before <= target) {
+  // The owner is the last segment that holds mass and starts at or below the target (the first segment with mass
+  // starts at exactly 0), and its pick a column that holds mass.  A test on the scanned values alone
+  // (before <= target < incl) let a segment of masked columns own the pick near u = 1: each lane's inclusive value
+  // is summed in its own order, so it can exceed its neighbour's by rounding with nothing added; and the walk below
+  // sums in yet another order, so it may not pass the target and must not fall back on a masked last column.
+  if (part > 0.f && before <= target) atomicMax(&owner, static_cast<int>(threadIdx.x));
+  __syncthreads();
+  if (owner == static_cast<int>(threadIdx.x)) {
     float run = before;
-    int idx = s1 - 1;
+    int idx = -1, last_live = s0;
     for (int i = s0; i < s1; ++i) {
-      run += __expf(row[i] - mx);
+      const float e = __expf(row[i] - mx);
+      if (e > 0.f) last_live = i;
+      run += e;
       if (run > target) { idx = i; break; }
     }
-    atomicMin(&pick, idx);
+    pick = idx >= 0 ? idx : last_live;
   }
   __syncthreads();
   const int r = pick;

@@ -269,20 +269,27 @@ __global__ __launch_bounds__(kThreads, 1) void su_sample_kernel(
       if (wv >= nwaves_valid) wave_off = off;
     }
     if (wv == owner_wave) {
-      float run = wave_off + incl - local;  // exclusive prefix of this thread's chunk
-      const bool cand = n_base < n1 && run <= target;
+      // exclusive prefix of this thread's chunk (the wave's first chunk with mass: wave_off exactly, <= target)
+      float run = wave_off + (incl - local);
+      // only a chunk that holds mass can own the pick, and inside it only an entity that does: this prefix is
+      // not summed in the scan's order, so near u = 1 it can round to <= target in a chunk of masked entities behind
+      // the last live one (or never pass target inside the owner's chunk), which drew the masked end token at step 0
+      const bool cand = n_base < n1 && local > 0.f && run <= target;
       const unsigned long long bal = __ballot(cand);
       const int owner = 63 - __builtin_clzll(bal | 1ull);
       if ((tid & 63) == owner) {
-        int pick = -1;
+        int pick = -1, last_live = -1;
 #pragma unroll
         for (int k = 0; k < kChunk; ++k) {
-          if (n_base + k < n1 && pick < 0) {
-            run += es[k];
-            if (run > target) pick = n_base + k;
+          if (n_base + k < n1) {
+            if (es[k] > 0.f) last_live = n_base + k;
+            if (pick < 0) {
+              run += es[k];
+              if (run > target) pick = n_base + k;
+            }
           }
         }
-        if (pick < 0) pick = min(n_base + kChunk, n1) - 1;
+        if (pick < 0) pick = last_live;
         s_result = pick;
       }
     }
@@ -629,7 +636,13 @@ __global__ __launch_bounds__(kWThreads, 1) void su_sample_wide_kernel(
     if (wv == owner_wave) {
       const float scale = __expf(mw - m);
       const float run = wave_off + (incl - es) * scale;     // exclusive prefix of this entity
-      const unsigned long long bal = __ballot(n < n1 && run <= target);
+      // only a lane that holds mass can own the pick: a masked lane's prefix is its own inclusive scan value, summed
+      // in another tree than the wave total, so near u = 1 it can lie an ulp below the total and at or below the
+      // target, which drew the masked end token at step 0 when it sat inside a 16-lane row.  The wave's first lane
+      // with mass has run == wave_off <= target, so an owner always exists.  (In a wave of masked lanes only, es is
+      // 1 in the wave's own scale and its total 0 in the common one: its offset equals the next wave's, which then
+      // owns, or it is the last wave and starts at the total, above every target.)
+      const unsigned long long bal = __ballot(n < n1 && es > 0.f && run <= target);
       const int owner = 63 - __builtin_clzll(bal | 1ull);
       if (lane == owner) s_result = n;
     }

@@ -2059,6 +2059,8 @@ def test_target_unit_fused_matches_torch(edtype):
     u = torch.rand(B, device=DEV)
     with torch.no_grad():
         key = head.key_fc(ent.float()).to(edtype)
+        # the head falls back to torch when the fused op returns None: it must not, here
+        assert ops.target_unit_sample(emb, head.query_fc1[0], head.query_fc2[0], key, en, 0.7, u) is not None
         lf, af = head(emb, ent, en, 0.7, u=u, key=key)
         ops.set_native(False)
         try:
@@ -2069,6 +2071,97 @@ def test_target_unit_fused_matches_torch(edtype):
     assert torch.equal(valid, lf > -1e8)
     assert _err(lf[valid], lr_[valid]) < 2e-4 * max(1.0, lr_[valid].abs().max().item())
     _same_or_boundary(af.cpu(), ar_.cpu(), lr_.cpu(), u.cpu())
+
+
+U_LAST = 1 - 2.0 ** -24         # the largest fp32 uniform
+
+
+def _valid_picks(act, logits, u):
+    """Every sampled index is an unmasked column whose interval of the row's float64 CDF, widened by the 1e-5 of
+    _same_or_boundary, holds the row's uniform: each pick is judged, none is excused."""
+    act, logits, u = act.cpu(), logits.cpu(), u.cpu()
+    cdf = torch.cumsum(torch.softmax(logits.double(), -1), -1)
+    for i, r in enumerate(act.tolist()):
+        assert 0 <= r < logits.shape[1] and float(logits[i, r]) > -1e8, (i, r)
+        lo = float(cdf[i, r - 1]) if r else 0.0
+        assert lo - 1e-5 <= float(u[i]) <= float(cdf[i, r]) + 1e-5, (i, r, float(u[i]), lo, float(cdf[i, r]))
+
+
+def _forced_uniforms(ref):
+    """One uniform per row of the masked reference logits ``ref`` [B, C], by row index mod 4: 0, the largest fp32
+    uniform, the float64 CDF edge behind the row's middle live column, and that behind its first live column."""
+    cdf = torch.cumsum(torch.softmax(ref.double().cpu(), -1), -1)
+    u = torch.zeros(ref.shape[0])
+    for i in range(ref.shape[0]):
+        live = torch.nonzero(ref[i].cpu() > -1e8).flatten()
+        u[i] = (0.0, U_LAST, float(cdf[i, live[len(live) // 2]]), float(cdf[i, live[0]]))[i % 4]
+    return u.clamp(max=U_LAST).to(ref.device)
+
+
+@pytest.mark.parametrize('masked', ['lens', 'shared'])
+@pytest.mark.parametrize('C', [1, 255, 256, 257, 513, 24577])
+def test_head_sample_forced_uniforms(C, masked):
+    """heads.hip sample_row at the uniforms torch.rand does not draw - 0, 1 - 2^-24 and exact CDF edges - on rows
+    whose leading and trailing columns are masked, at the widths where a thread's segment goes from 1 to 2 columns
+    (256 / 257), at 3 (513) and one past the rows staged in LDS (24,577, read from global memory).  1, 2 and 5
+    trailing masked columns put the last live column first, in the middle and last in its thread's segment."""
+    from applestar_amd import ops
+    from applestar_amd.models.heads import NEG
+    torch.manual_seed(C)
+    lead = min(3, max(C - 8, 0))
+    trails = [t for t in (1, 2, 5) if lead + t < C] or [0]
+    cols = torch.arange(C, device=DEV)
+    for k, group in enumerate([trails] if masked == 'lens' else [[t] for t in trails]):
+        B = 4 * len(group)
+        logits = torch.randn(B, C, device=DEV) * 3
+        trail = torch.tensor(group, device=DEV).repeat_interleave(4)
+        valid = (cols[None] >= lead) & (cols[None] < C - trail[:, None])
+        mask = lens = None
+        if masked == 'lens':      # the length masks the tail; the head of the row is masked by its own logits
+            lens = C - trail
+            logits[:, :lead] = NEG
+        else:
+            mask = valid[0]
+        ref = (logits / 0.8).masked_fill(~valid, NEG)
+        u = _forced_uniforms(ref)
+        with torch.no_grad():
+            out, act, _ = ops.head_sample(logits, 0.8, mask=mask, lens=lens, u=u)
+        assert torch.equal(out > -1e8, valid)
+        assert _err(out[valid], ref[valid]) < 1e-5 * ref[valid].abs().max().item() + 1e-6
+        _valid_picks(act, out, u)
+        assert bool(valid[torch.arange(B), act].all())
+
+
+@pytest.mark.parametrize('edtype,kdtype', [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
+                                           (torch.float32, torch.bfloat16), (torch.bfloat16, torch.float32)])
+@pytest.mark.parametrize('N', [1, 65, 512])
+def test_target_unit_forced_uniforms(N, edtype, kdtype):
+    """heads.hip target_unit_sample at 0, 1 - 2^-24 and exact CDF edges, with 0, 1 and 2 trailing entities masked by
+    entity_num (N = 512: two entities per thread), for every embedding / key dtype pair."""
+    from applestar_amd import ops
+    from applestar_amd.models.heads import TargetUnitHead
+    torch.manual_seed(N)
+    head = TargetUnitHead().to(DEV)
+    trails = [t for t in (0, 1, 2) if t < N]
+    B = 4 * len(trails)
+    emb = torch.randn(B, 1024, device=DEV).to(edtype)
+    key = torch.randn(B, N, 32, device=DEV).to(kdtype)
+    en = N - torch.tensor(trails, device=DEV).repeat_interleave(4)
+    with torch.no_grad():
+        ops.set_native(False)
+        try:
+            ref, _ = head(emb.float(), None, en, 0.7, u=torch.zeros(B, device=DEV), key=key.float())
+        finally:
+            ops.set_native(True)
+        u = _forced_uniforms(ref)
+        # the fused op itself: the head falls back to torch when it returns None, which would pass unnoticed
+        fused = ops.target_unit_sample(emb, head.query_fc1[0], head.query_fc2[0], key, en, 0.7, u)
+        assert fused is not None
+        lf, af = fused
+    valid = torch.arange(N, device=DEV)[None] < en[:, None]
+    assert torch.equal(lf > -1e8, valid) and torch.equal(ref > -1e8, valid)
+    assert _err(lf[valid], ref[valid]) < 2e-4 * max(1.0, ref[valid].abs().max().item())
+    _valid_picks(af, lf, u)
 
 
 def test_wgrad_f32_long_reduction_is_deterministic():
